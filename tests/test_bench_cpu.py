@@ -35,6 +35,34 @@ def test_roofline_block_arithmetic():
     assert bench.TILE_PIPE_CYCLES["bf16x6"]["decode_lattice"] == 480 * 32 + 16 * 64 and abs(bench.PEAK_X6_FP32_EQUIV_TFLOPS - 416.67) < 0.01
 
 
+def test_dump_outputs_fits_the_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: groups that fit are written whole; the others share what is left of the byte limit as a seeded sample of their rows (the
+    same rows on every run, in row order, their indices beside them); the last output of each stream is the last non-None one handed back."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    rng = np.random.default_rng(3)
+    groups = {"frame": {"frame_triangles": rng.random((500, 3, 3), dtype=np.float32), "frame_triangle_voxel_ids": np.arange(500.0)},
+              "mesh": {"mesh_triangles": rng.random((40000, 3, 3), dtype=np.float32), "mesh_triangle_voxel_ids": np.arange(40000.0)},
+              "map": {"map_latent_vecs": rng.random((3000, 29), dtype=np.float32)}}
+    limit = 1 << 20
+    shapes = bench.dump_outputs(tmp_path / "a", groups, limit=limit)
+    bench.dump_outputs(tmp_path / "b", groups, limit=limit)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(f"{k}.npy" for k in shapes) and "mesh_sample_rows.npy" in files and "frame_sample_rows.npy" not in files
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= limit
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "frame_triangles.npy"), groups["frame"]["frame_triangles"])
+    rows = np.load(tmp_path / "a" / "mesh_sample_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 40000 and (np.diff(rows) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "mesh_triangle_voxel_ids.npy"), rows.astype(np.float64))
+    # everything under the limit: no sample
+    assert "mesh_sample_rows" not in bench.dump_outputs(tmp_path / "c", groups)
+    assert bench.last_output([(1, 2, 3), None], 1) == [(1, 2, 3)] and bench.last_output([[(1,), (2,)], [None, (3,)]], 2) == [(1,), (3,)]
+
+
 def _run(args, env_extra):
     env = dict(os.environ, **env_extra)
     env.pop("RANK", None)

@@ -12,6 +12,6 @@ timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch20 -o 
 timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write20 -o w -- $B $K20 > $O/pmc_write20.log 2>&1
 python tools/pmc_summary.py $(find $O/pmc_fetch20 -name "*counter_collection.csv" | head -1) $(find $O/pmc_write20 -name "*counter_collection.csv" | head -1) $O/pmc_hbm_k20.json --last 20 > $O/pmc_summary20.log 2>&1
 rm -rf $O/pmc_mfma20 $O/pmc_fetch20 $O/pmc_write20
-for i in 1 2 3; do timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_k20_full_$i.json 2> $O/bench_k20_full_$i.err; done
+for i in 1 2 3; do timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20_full_$i.json 2> $O/bench_k20_full_$i.err; done
 for i in 1 2 3; do python tools/bench_query.py > $O/bench_query_$i.json 2>/dev/null; done
 cat $O/pmc_mfma20_summary.log; head -20 $O/kernel_stats_k20.md

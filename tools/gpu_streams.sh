@@ -4,7 +4,7 @@
 tag=${1:-s}; out=gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests/test_gpu_stream.py -m gpu -q -x 2>&1 | tail -15 | cut -c1-400
-timeout 600 python bench.py --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err; tail -3 $out/bench_200.err
+timeout 600 python bench.py --full --no-cpu-baseline > $out/bench_200.json 2> $out/bench_200.err; tail -3 $out/bench_200.err
 python - $out/bench_200.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-final1}; mkdir -p $O
 B="python bench.py"
 # ---- the default invocation (200 steps) ----
-timeout 600 $B > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 $B --full > $O/bench_n1.json 2> $O/bench_n1.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- $B --no-cpu-baseline --no-secondary > $O/trace_bench.log 2>&1
 python tools/rocpd_stats.py $(find $O/trace -name "*.db" | head -1) --after-nth k_prune_mark 14 --frames 200 > $O/kernel_stats.md 2>&1
 python tools/rocpd_stats.py $(find $O/trace -name "*.db" | head -1) --after-nth k_prune_mark 160 --frames 50 > $O/kernel_stats_steady.md 2>&1
@@ -19,7 +19,7 @@ rm -rf $O/trace
 timeout 300 $B --no-cpu-baseline --no-secondary --overlap 0 --steps 20 --warmup 5 > $O/bench_k20_one_queue.json 2> $O/bench_k20_one_queue.err
 # ---- the DRIVER's invocation: --steps 20 --warmup 5 (map-building transient) ----
 K20="--steps 20 --warmup 5 --no-cpu-baseline"
-timeout 300 $B $K20 > $O/bench_k20.json 2> $O/bench_k20.err
+timeout 300 $B $K20 --full > $O/bench_k20.json 2> $O/bench_k20.err
 # (the rocprofv3 passes of this invocation run WITHOUT the secondary legs — the S-streams-per-GPU rates that follow the timed region since round 4:
 # their streams' first frames launch the same kernels and would land in "the last 20 dispatches"; the timed region itself is identical)
 K20="$K20 --no-secondary"
@@ -74,7 +74,7 @@ timeout 400 rocprofv3 --kernel-trace --stats -d $O/trace_t1 -o bench -- $B --mod
 python tools/rocpd_stats.py $(find $O/trace_t1 -name "*.db" | head -1) --after-nth k_prune_mark 14 --frames 100 > $O/kernel_stats_tiled_n1.md 2>&1
 rm -rf $O/trace_lb8 $O/trace_t1
 # ---- the rest ----
-for c in c1 c2; do timeout 300 $B --config $c --no-cpu-baseline --steps 50 > $O/bench_$c.json 2> $O/bench_$c.err; done
+for c in c1 c2; do timeout 300 $B --config $c --full --no-cpu-baseline --steps 50 > $O/bench_$c.json 2> $O/bench_$c.err; done
 DIF_FORCE_DIST=1 timeout 300 $B --no-cpu-baseline --no-secondary > $O/bench_rccl_1rank.json 2> $O/bench_rccl_1rank.err
 DIF_FORCE_DIST=1 timeout 300 $B --no-cpu-baseline --no-secondary --rccl-before-clock 1 > $O/bench_rccl_1rank_before_clock.json 2> $O/bench_rccl_1rank_before_clock.err
 timeout 900 python tools/stress_full_occupancy.py --n 128 --reps 2 > $O/stress_full.json 2> $O/stress_full.err
