@@ -277,13 +277,17 @@ __device__ __forceinline__ float pose_row(const float* T, int j, float x, float 
 
 // Row of a decode tile: which sample lane `col` of tile `tile` works on, where its result goes, and its input fragment
 // xin[t] = x0[2t + half] with x0 = [latent 29 | xyz 3] (the natural k order of layer 0 and of the skip input).
-struct DecodeRow { bool live; int64_t out_idx; float px, py, pz; };
+// bad: an explicit row (mode 2) that holds a NaN or an infinity.  Its outputs are stored as NaN, which is what the reference's float
+// arithmetic makes of such a row; computed, the row would come out FINITE (relu1 turns a NaN with its sign bit set into 0, and the
+// bf16 slicing hands the matrix pipe NaNs of either sign).  Taken at the load, applied at the store: the tiles never look at it.
+// (k_decode_x6 sits at 256 VGPRs with this flag, the ceiling of its two waves per SIMD, without scratch: one more live value there spills.)
+struct DecodeRow { bool live; int64_t out_idx; float px, py, pz; bool bad; };
 // DENSE: the instantiation for mode 4 only (and the others without it): the dense query's pose, counts and threshold are twelve more kernel arguments
 // held in scalar registers, which the general kernels do not have to spare (k_decode_x6 spilled seven vector registers with both in one body).
 template <bool DENSE = false>
 __device__ __forceinline__ DecodeRow decode_row_input(const DecodeArgs& A, int64_t tile, int col, int half, int res3, int tiles_per_voxel, int64_t n_rows,
                                                       f16v& xin) {
-    DecodeRow R{false, 0, 0.f, 0.f, 0.f};
+    DecodeRow R{false, 0, 0.f, 0.f, 0.f, false};
     const float* lat_row = nullptr;
     const float* row32 = nullptr;
     if (!DENSE && A.mode == 0) {
@@ -351,6 +355,15 @@ __device__ __forceinline__ DecodeRow decode_row_input(const DecodeArgs& A, int64
         }
         xin[t] = v;
     }
+    if constexpr (!DENSE) {
+        if (A.mode == 2) {                          // (wave-uniform) each half holds 16 of the row's 32 values
+            unsigned nf = 0;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) nf |= ((__float_as_uint(xin[t]) & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;
+            nf |= (unsigned)__shfl_xor((int)nf, 32);
+            R.bad = nf != 0;
+        }
+    }
     return R;
 }
 
@@ -390,16 +403,17 @@ __global__ void __launch_bounds__(GRAD ? 256 : 512, GRAD ? 1 : 2) k_decode(Decod
             float gx, gy, gz;
             decoder_tile_grad(lds, wfwd, wbwd, xin, lane, sdf, sd, gx, gy, gz);
             if (live && half == 1) {
-                A.out_grad[out_idx * 3 + 0] = gx * A.grad_scale;      // d rel / d xyz = 1 / voxel_size (map.py:565,575)
-                A.out_grad[out_idx * 3 + 1] = gy * A.grad_scale;
-                A.out_grad[out_idx * 3 + 2] = gz * A.grad_scale;
+                const float gs = R.bad ? __builtin_nanf("") : A.grad_scale;      // d rel / d xyz = 1 / voxel_size (map.py:565,575)
+                A.out_grad[out_idx * 3 + 0] = gx * gs;
+                A.out_grad[out_idx * 3 + 1] = gy * gs;
+                A.out_grad[out_idx * 3 + 2] = gz * gs;
             }
         } else {
             decoder_tile(lds, wfwd, xin, lane, sdf, sd);
         }
         if (live) {
-            if (half == 0) A.out_sdf[out_idx] = A.sign * sdf;
-            else A.out_std[out_idx] = sd;
+            if (half == 0) A.out_sdf[out_idx] = R.bad ? __builtin_nanf("") : A.sign * sdf;
+            else A.out_std[out_idx] = R.bad ? __builtin_nanf("") : sd;
         }
     }
 }
@@ -434,8 +448,8 @@ __global__ void __launch_bounds__(512, 1) k_decode_x6(DecodeArgs A, const float*
         float sdf, sd;
         decoder_tile_x6(lds, wfwd, wun, xin, lane, sdf, sd);
         if (live) {
-            if (half == 0) A.out_sdf[out_idx] = A.sign * sdf;
-            else A.out_std[out_idx] = sd;
+            if (half == 0) A.out_sdf[out_idx] = R.bad ? __builtin_nanf("") : A.sign * sdf;
+            else A.out_std[out_idx] = R.bad ? __builtin_nanf("") : sd;
         }
     }
 }
@@ -466,12 +480,13 @@ __global__ void __launch_bounds__(GRAD_X6_THREADS, 1) k_decode_grad_x6(DecodeArg
         float sdf, sd, gx, gy, gz;
         decoder_tile_grad_x6<PF>(lds, wfwd, wun, wbw, xin, lane, sdf, sd, gx, gy, gz);
         if (R.live) {
-            if (half == 0) A.out_sdf[R.out_idx] = A.sign * sdf;
+            if (half == 0) A.out_sdf[R.out_idx] = R.bad ? __builtin_nanf("") : A.sign * sdf;
             else {
-                A.out_std[R.out_idx] = sd;
-                A.out_grad[R.out_idx * 3 + 0] = gx * A.grad_scale;      // d rel / d xyz = 1 / voxel_size (map.py:565,575)
-                A.out_grad[R.out_idx * 3 + 1] = gy * A.grad_scale;
-                A.out_grad[R.out_idx * 3 + 2] = gz * A.grad_scale;
+                const float gs = R.bad ? __builtin_nanf("") : A.grad_scale;      // d rel / d xyz = 1 / voxel_size (map.py:565,575)
+                A.out_std[R.out_idx] = R.bad ? __builtin_nanf("") : sd;
+                A.out_grad[R.out_idx * 3 + 0] = gx * gs;
+                A.out_grad[R.out_idx * 3 + 1] = gy * gs;
+                A.out_grad[R.out_idx * 3 + 2] = gz * gs;
             }
         }
     }

@@ -562,6 +562,11 @@ __global__ void __launch_bounds__(512, X6 ? 1 : 2) k_encode_rows(const float* __
             x1 = half ? p[3] : p[2];
             x2 = half ? p[5] : p[4];
         }
+        // a row that holds a NaN or an infinity is stored as NaN (what the reference's float arithmetic makes of it; computed, relu1 and
+        // the bf16 slicing would hand back finite values): flag taken at the load, applied at the store
+        unsigned nf = (((__float_as_uint(x0) & 0x7f800000u) == 0x7f800000u) || ((__float_as_uint(x1) & 0x7f800000u) == 0x7f800000u) ||
+                       ((__float_as_uint(x2) & 0x7f800000u) == 0x7f800000u)) ? 1u : 0u;
+        nf |= (unsigned)__shfl_xor((int)nf, 32);
         f16v o;
         if constexpr (X6) o = encoder_tile_x6(lds, x0, x1, x2, lane);
         else o = encoder_tile(lds, x0, x1, x2, lane);
@@ -569,7 +574,7 @@ __global__ void __launch_bounds__(512, X6 ? 1 : 2) k_encode_rows(const float* __
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 int f = (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (f < L) out[row * L + f] = o[r];
+                if (f < L) out[row * L + f] = nf ? __builtin_nanf("") : o[r];
             }
         }
     }

@@ -59,6 +59,19 @@ def check_state(m, g, f, om=None):
         assert np.abs(m.latent_vecs[:n].cpu().numpy() - om.latent_vecs[:n]).max() < LATENT_TOL
 
 
+def check_state_oracle(m, om):
+    """check_state against the oracle alone (weights the goldens were not recorded with): integer state bit for bit, latents within LATENT_TOL"""
+    n = m.n_occupied
+    assert n == om.n_occupied
+    assert np.array_equal(m.indexer.cpu().numpy(), om.indexer)
+    assert np.array_equal(m.latent_vecs_pos[:n].cpu().numpy(), om.latent_vecs_pos[:n])
+    assert np.array_equal(m.voxel_obs_count[:n].cpu().numpy(), om.voxel_obs_count[:n])
+    assert np.array_equal(m.updated_vec_id.cpu().numpy(), om.updated_vec_id)
+    d = np.abs(m.latent_vecs[:n].cpu().numpy() - om.latent_vecs[:n]).max()
+    print(f"  n_occupied={n} latent maxdiff vs oracle {d:.3e} counters={m.last_counters}")
+    assert d < LATENT_TOL
+
+
 def sort_tris(tri, tid):
     """canonical, permutation-invariant order: (voxel id, quantised centroid)"""
     c = np.round(tri.mean(axis=1) * 4096).astype(np.int64)
@@ -67,6 +80,12 @@ def sort_tris(tri, tid):
 
 @pytest.mark.parametrize("name", ["seq_small", "seq_room16", "seq_c2", "seq_c3"])
 def test_sequence_vs_golden_and_oracle(name, gpu_model, oracle_net):
+    run_sequence(name, gpu_model, oracle_net, golden=True)
+
+
+def run_sequence(name, gpu_model, oracle_net, golden):
+    """The fixture's frames through the GPU map and through the oracle stepped on the same inputs.  golden: also against the vectors
+    recorded from the reference (they belong to the shipped weights; tests/test_gpu_mlp_envelope.py runs other weight sets without)."""
     from oracle import difusion_oracle as O
     scene, cfg, intr = CASES[name]
     g = np.load(GOLDEN / f"{name}.npz")
@@ -76,9 +95,12 @@ def test_sequence_vs_golden_and_oracle(name, gpu_model, oracle_net):
         xyz, nrm = frame_inputs(g, name, f)
         mask = m.integrate_keyframe(torch.from_numpy(xyz).to(DEV), torch.from_numpy(nrm).to(DEV))
         omask = om.integrate_keyframe(xyz, nrm)
-        assert np.array_equal(np.packbits(mask.cpu().numpy()), g[f"f{f}_unq_mask"])
         assert np.array_equal(mask.cpu().numpy(), omask)
-        check_state(m, g, f, om)
+        if golden:
+            assert np.array_equal(np.packbits(mask.cpu().numpy()), g[f"f{f}_unq_mask"])
+            check_state(m, g, f, om)
+        else:
+            check_state_oracle(m, om)
         assert m.last_counters["M"] == om.last_stats["M"] and m.last_counters["C"] == om.last_stats["C"]
 
         # ---- extract: GPU pipeline, then the oracle on ITS state -------------------------------------------
@@ -86,9 +108,12 @@ def test_sequence_vs_golden_and_oracle(name, gpu_model, oracle_net):
         new_T = m.last_counters["T"]
         tens = m._xbuf[1]
         K, B = m.last_counters["K"], m.last_counters["B"]
-        assert np.array_equal(tens["valid_blocks"][:K].cpu().numpy(), g[f"f{f}_mc_valid_blocks"])
-        assert B == int(g[f"f{f}_mc_B"])
         oa = om.extract_prepare(4)
+        if golden:
+            assert np.array_equal(tens["valid_blocks"][:K].cpu().numpy(), g[f"f{f}_mc_valid_blocks"])
+            assert B == int(g[f"f{f}_mc_B"])
+        else:
+            assert np.array_equal(tens["valid_blocks"][:K].cpu().numpy(), oa["valid_blocks"]) and B == len(oa["occupied_vec_id"])
         assert np.array_equal(tens["occ_slot"][:B].cpu().numpy(), oa["occupied_vec_id"])
         cs = tens["cube_sdf"][:B].cpu().numpy(); cd = tens["cube_std"][:B].cpu().numpy()
         sel = g[f"f{f}_mc_cube_sel"] if f"f{f}_mc_cube_sel" in g else np.arange(B)
@@ -102,7 +127,8 @@ def test_sequence_vs_golden_and_oracle(name, gpu_model, oracle_net):
         print(f"  frame {f}: K={K} B={B} VH={m.last_counters['VH']} (oracle {oa['n_rows_refine']}) cube maxdiff sdf {ds[~flip].max():.2e} "
               f"std {dd[~flip].max():.2e} near-threshold {flip.sum()}")
         assert ds[~flip].max() < SDF_TOL and dd[~flip].max() < SDF_TOL
-        assert np.abs(cs[sel] - g[f"f{f}_mc_cube_sdf"])[~flip[sel]].max() < SDF_TOL
+        if golden:
+            assert np.abs(cs[sel] - g[f"f{f}_mc_cube_sdf"])[~flip[sel]].max() < SDF_TOL
         assert abs(m.last_counters["VH"] - oa["n_rows_refine"]) <= flip.sum()
         # marching cubes on the GPU's own cubes through the C oracle: isolates the MC kernel
         wt, wi, ws = O.marching_cubes_interp(oa["indexer"], oa["valid_blocks"], oa["vec_batch_mapping"], cs, cd, int(4e6), om.n_xyz, 0.15)
@@ -112,14 +138,20 @@ def test_sequence_vs_golden_and_oracle(name, gpu_model, oracle_net):
         gt = ntri.cpu().numpy()
         want = (wt * np.float32(cfg.voxel_size)).astype(np.float32) + om.bound_min
         assert np.array_equal(nid.cpu().numpy(), wi)
-        assert np.abs(gt - want).max() < 1e-5
-        assert np.abs(nstd.cpu().numpy() - ws).max() < 1e-5
-        assert new_T > 0
+        if golden or new_T:                 # (a foreign decoder need not put a zero crossing into this scene: no triangles, nothing to compare)
+            assert np.abs(gt - want).max() < 1e-5
+            assert np.abs(nstd.cpu().numpy() - ws).max() < 1e-5
+        assert new_T > 0 or not golden
     # ---- get_sdf ---------------------------------------------------------------------------------------------
     sdf, std, qmask = m.get_sdf(torch.from_numpy(g["probe_xyz"]).to(DEV))
-    assert np.array_equal(qmask.cpu().numpy(), g["probe_mask"])
-    assert np.abs(sdf.cpu().numpy() - g["probe_sdf"]).max() < SDF_TOL
-    assert np.abs(std.cpu().numpy() - g["probe_std"]).max() < SDF_TOL
+    if golden:
+        assert np.array_equal(qmask.cpu().numpy(), g["probe_mask"])
+        assert np.abs(sdf.cpu().numpy() - g["probe_sdf"]).max() < SDF_TOL
+        assert np.abs(std.cpu().numpy() - g["probe_std"]).max() < SDF_TOL
+    else:
+        osdf, ostd, omask = om.get_sdf(g["probe_xyz"])
+        assert np.array_equal(qmask.cpu().numpy(), omask)
+        assert np.abs(sdf.cpu().numpy() - osdf).max() < SDF_TOL and np.abs(std.cpu().numpy() - ostd).max() < SDF_TOL
 
 
 @pytest.mark.parametrize("pipe", ["bf16x6", "f32"])
