@@ -79,6 +79,17 @@ class DifSdfHg(ctypes.Structure):
                 ("no_grad", c_int32)]
 
 
+class DifPhotoPyramid(ctypes.Structure):
+    """include/difusion.h: dif_photo_pyramid_t"""
+    _fields_ = [("intensity", c_void_p * 3), ("depth", c_void_p * 3), ("gradient", c_void_p * 3)]
+
+
+class DifRgbHg(ctypes.Structure):
+    """include/difusion.h: dif_rgb_hg_t"""
+    _fields_ = [("krkinv", c_float * 9), ("kt", c_float * 3), ("intr", c_float * 4), ("min_grad_scale", c_float), ("max_depth_delta", c_float),
+                ("weight", c_float), ("robust_kernel", c_int32), ("robust_k", c_float), ("no_grad", c_int32)]
+
+
 SIGNATURES = {
     "dif_version": (c_int32, []),
     "dif_build_id": (ctypes.c_char_p, []),
@@ -149,6 +160,13 @@ SIGNATURES = {
     "dif_sdf_hg_workspace_bytes": (c_int64, [c_int64]),
     "dif_sdf_hg": (c_int32, [POINTER(DifMap), POINTER(DifWeights), c_void_p, c_int64, POINTER(DifSdfHg), c_void_p, c_int64, c_void_p, c_void_p,
                              c_int64, c_void_p]),
+    "dif_gradient_xy": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "dif_photo_pyramid": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, POINTER(DifPhotoPyramid), c_void_p]),
+    "dif_rgb_odometry": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(DifRgbHg), c_void_p, c_void_p,
+                                   c_void_p]),
+    "dif_rgb_hg_workspace_bytes": (c_int64, []),
+    "dif_rgb_hg": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(DifRgbHg), c_void_p, c_int64, c_void_p,
+                             c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

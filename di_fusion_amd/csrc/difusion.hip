@@ -135,6 +135,7 @@ inline int grid_for(int64_t n, int per_block = DIF_BLOCK, int max_blocks = 4096)
 #include "kernels_cloud.hip.h"
 #include "kernels_optimize.hip.h"
 #include "kernels_track.hip.h"
+#include "kernels_photo.hip.h"
 #include "kernels_litmus.hip.h"
 
 }  // namespace
@@ -1719,6 +1720,83 @@ int dif_sdf_hg(const dif_map_t* map, const dif_weights_t* w, const float* obs_xy
     } else if (hipMemsetAsync(ticket, 0, sizeof(int), s) != hipSuccess) return DIF_ELAUNCH;
     hipLaunchKernelGGL(k_sdf_hg_reduce, dim3(grid_for(N, 2 * DIF_BLOCK, HG_BLOCKS)), dim3(DIF_BLOCK), 0, s, (int)N, obs_xyz, (const float*)(b + L.sdf),
                        (const float*)(b + L.std_), (const float*)grad, a, (double*)(b + L.partial), ticket, out, out_host, seq);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- the tracker's photometric term (photometric.cu, tracker.py:41-56, 131-172) ---------------------------------------------------------
+int dif_gradient_xy(const float* intensity, int32_t H, int32_t W, float* out, void* stream) {
+    if (!intensity || !out || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    hipLaunchKernelGGL(k_gradient_xy, dim3(grid_for((int64_t)H * W)), dim3(DIF_BLOCK), 0, (hipStream_t)stream, intensity, out, H, W);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int dif_photo_pyramid(const float* rgb, const float* depth, int32_t H, int32_t W, const dif_photo_pyramid_t* out, void* stream) {
+    if (!depth || !out || H < 4 || W < 4 || (int64_t)H * W >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    for (int l = 0; l < 3; ++l)
+        if (!out->intensity[l] || !out->depth[l] || !out->gradient[l]) return DIF_EINVAL;
+    int h = H, w = W;
+    for (int l = 0; l < 3; ++l) {
+        PhotoLevelArgs a = {};
+        a.H = l == 0 ? h : h / 2; a.W = l == 0 ? w : w / 2; a.Hs = h; a.Ws = w;
+        a.rgb = l == 0 ? rgb : nullptr;
+        a.src_I = l == 0 ? (rgb ? nullptr : out->intensity[0]) : out->intensity[l - 1];
+        a.src_D = l == 0 ? depth : out->depth[l - 1];
+        a.sh = (float)a.Hs / (float)a.H; a.sw = (float)a.Ws / (float)a.W;
+        a.I = out->intensity[l]; a.D = out->depth[l]; a.G = out->gradient[l];
+        hipLaunchKernelGGL(k_photo_level, dim3((a.W + FE_TILE - 1) / FE_TILE, (a.H + FE_TILE - 1) / FE_TILE), dim3(FE_TILE * FE_TILE), 0,
+                           (hipStream_t)stream, a);
+        DIF_CHECK_LAUNCH();
+        h = a.H; w = a.W;
+    }
+    return DIF_OK;
+}
+
+namespace {
+struct RgbHgLayout { int64_t partial, ticket, total; };
+inline RgbHgLayout rgb_hg_layout() {
+    RgbHgLayout L;
+    int64_t o = 0;
+    L.partial = o; o = up256(o + (int64_t)HG_BLOCKS * HG_TERMS * 8);
+    L.ticket = o;  o = up256(o + 4);
+    L.total = o;
+    return L;
+}
+inline bool photo_args(const dif_rgb_hg_t* args, int32_t H, int32_t W, PhotoArgs& a) {
+    if (!args || H < 3 || W < 3 || (int64_t)H * W >= ((int64_t)1 << 31)) return false;
+    if (args->robust_kernel < 0 || args->robust_kernel > 2) return false;
+    for (int i = 0; i < 9; ++i) a.k[i] = args->krkinv[i];
+    for (int i = 0; i < 3; ++i) a.kt[i] = args->kt[i];
+    a.fx = args->intr[0]; a.fy = args->intr[1]; a.cx = args->intr[2]; a.cy = args->intr[3];
+    a.min_grad = args->min_grad_scale; a.max_dd = args->max_depth_delta;
+    a.robust = args->robust_kernel; a.rk = args->robust_k; a.no_grad = args->no_grad ? 1 : 0;
+    a.weight = (double)args->weight;
+    return true;
+}
+}  // namespace
+
+int dif_rgb_odometry(const float* prev_I, const float* prev_D, const float* cur_I, const float* cur_D, const float* cur_G, int32_t H, int32_t W,
+                     const dif_rgb_hg_t* args, float* f_out, float* J_out, void* stream) {
+    PhotoArgs a;
+    if (!prev_I || !prev_D || !cur_I || !cur_D || !cur_G || !f_out || !photo_args(args, H, W, a)) return DIF_EINVAL;
+    hipLaunchKernelGGL(k_rgb_odometry, dim3(grid_for((int64_t)H * W)), dim3(DIF_BLOCK), 0, (hipStream_t)stream, (int)H, (int)W, prev_I, prev_D, cur_I,
+                       cur_D, cur_G, a, f_out, J_out);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int64_t dif_rgb_hg_workspace_bytes(void) { return rgb_hg_layout().total; }
+
+int dif_rgb_hg(const float* prev_I, const float* prev_D, const float* cur_I, const float* cur_D, const float* cur_G, int32_t H, int32_t W,
+               const dif_rgb_hg_t* args, void* ws, int64_t ws_bytes, double* out, double* out_host, int64_t seq, void* stream) {
+    PhotoArgs a;
+    if (!prev_I || !prev_D || !cur_I || !cur_D || !cur_G || !out || !photo_args(args, H, W, a)) return DIF_EINVAL;
+    const RgbHgLayout L = rgb_hg_layout();
+    if (!ws || ws_bytes < L.total || ((uintptr_t)ws & 255) != 0) return DIF_EINVAL;
+    char* b = (char*)ws;
+    hipLaunchKernelGGL(k_rgb_hg, dim3(grid_for((int64_t)H * W, 2 * DIF_BLOCK, HG_BLOCKS)), dim3(DIF_BLOCK), 0, (hipStream_t)stream, (int)H, (int)W, prev_I,
+                       prev_D, cur_I, cur_D, cur_G, a, (double*)(b + L.partial), (int*)(b + L.ticket), out, out_host, seq);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

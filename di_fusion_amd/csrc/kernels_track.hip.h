@@ -76,26 +76,15 @@ __device__ __forceinline__ void hg_accumulate(double* acc, const HgArgs& a, cons
     for (int r = 0; r < 6; ++r) acc[21 + r] += (double)J[r] * (double)wf;
 }
 
+// The part of the reduction both terms of the tracker share (k_sdf_hg_reduce, k_rgb_hg): a thread's HG_TERMS sums -> the 44 numbers.
 // Fixed reduction tree (thread: grid-stride order; 16-lane row; workgroup: rows in order; grid: workgroups in order, summed by whichever workgroup
-// arrives last): the same inputs give the same 44 numbers, whatever the order the workgroups run in.
-__global__ void __launch_bounds__(DIF_BLOCK) k_sdf_hg_reduce(int N, const float* __restrict__ obs, const float* __restrict__ sdf, const float* __restrict__ std_,
-                                                           const float* __restrict__ grad, HgArgs a, double* partial, int* ticket, double* out,
-                                                           double* out_host, int64_t seq) {
+// arrives last): the same inputs give the same 44 numbers, whatever the order the workgroups run in.  `ticket` is 0 when the launch starts and is
+// left at 0.  WEIGHTED: the photometric term's scale, 1 / M * weight; otherwise 1 / M by division.
+template <bool WEIGHTED>
+__device__ __forceinline__ void hg_finish(const double (&acc)[HG_TERMS], double* partial, int* ticket, double* out, double* out_host, int64_t seq,
+                                          double weight) {
     __shared__ double red[DIF_BLOCK / 16][HG_TERMS];
     __shared__ int last;
-    double acc[HG_TERMS];
-#pragma unroll
-    for (int t = 0; t < HG_TERMS; ++t) acc[t] = 0.0;
-    // two points per thread and trip, their loads issued together (the decoder's outputs were written by other XCDs a moment ago: L2 misses)
-    const int stride = (int)(gridDim.x * blockDim.x);
-    for (int m = (int)(blockIdx.x * blockDim.x + threadIdx.x); m < N; m += 2 * stride) {
-        const int m1 = m + stride < N ? m + stride : m;
-        HgPoint p0, p1;
-        p0.load(m, obs, sdf, std_, grad, a.no_grad);
-        p1.load(m1, obs, sdf, std_, grad, a.no_grad);
-        hg_accumulate(acc, a, p0);
-        if (m1 != m) hg_accumulate(acc, a, p1);
-    }
     // 16-lane rows summed on the VALU (four DPP row shifts: lane 15 of a row ends with the row's sum; a 64-bit __shfl costs two trips through
     // the LDS crossbar and there are 28 values), the 16 row sums of the workgroup added in order by one thread per term
     const int lane = lane_id(), wid = threadIdx.x >> 6;
@@ -150,7 +139,7 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_sdf_hg_reduce(int N, const float*
         tot[threadIdx.x] = v;
     }
     __syncthreads();
-    const double Mv = tot[28];                   // the number of valid points; the sums are scaled by 1 / M (tracker.py:209-218)
+    const double Mv = tot[28];                   // the number of valid points; the sums are scaled by 1 / M (tracker.py:209-218) or by 1 / M * weight (tracker.py:165)
     if (threadIdx.x < 44) {
         double v;
         const int e = (int)threadIdx.x;
@@ -161,7 +150,10 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_sdf_hg_reduce(int N, const float*
         } else if (e < 42) v = tot[21 + (e - 36)];
         else if (e == 42) v = tot[27];
         else v = Mv;
-        if (e < 43) v = Mv > 0.0 ? v / Mv : 0.0;
+        if (e < 43) {
+            if (WEIGHTED) v = Mv > 0.0 ? v * (1.0 / Mv * weight) : 0.0;
+            else v = Mv > 0.0 ? v / Mv : 0.0;
+        }
         out[e] = v;
         if (out_host) {                          // written through to the host and acknowledged ...
             __hip_atomic_store(out_host + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -173,4 +165,23 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_sdf_hg_reduce(int N, const float*
         *ticket = 0;
         if (out_host) __hip_atomic_store((int64_t*)out_host + 44, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);       // ... before the sequence number follows
     }
+}
+
+__global__ void __launch_bounds__(DIF_BLOCK) k_sdf_hg_reduce(int N, const float* __restrict__ obs, const float* __restrict__ sdf, const float* __restrict__ std_,
+                                                           const float* __restrict__ grad, HgArgs a, double* partial, int* ticket, double* out,
+                                                           double* out_host, int64_t seq) {
+    double acc[HG_TERMS];
+#pragma unroll
+    for (int t = 0; t < HG_TERMS; ++t) acc[t] = 0.0;
+    // two points per thread and trip, their loads issued together (the decoder's outputs were written by other XCDs a moment ago: L2 misses)
+    const int stride = (int)(gridDim.x * blockDim.x);
+    for (int m = (int)(blockIdx.x * blockDim.x + threadIdx.x); m < N; m += 2 * stride) {
+        const int m1 = m + stride < N ? m + stride : m;
+        HgPoint p0, p1;
+        p0.load(m, obs, sdf, std_, grad, a.no_grad);
+        p1.load(m1, obs, sdf, std_, grad, a.no_grad);
+        hg_accumulate(acc, a, p0);
+        if (m1 != m) hg_accumulate(acc, a, p1);
+    }
+    hg_finish<false>(acc, partial, ticket, out, out_host, seq, 1.0);
 }

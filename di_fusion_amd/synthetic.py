@@ -200,6 +200,51 @@ def transform_points(p: torch.Tensor, R: torch.Tensor, t: Optional[torch.Tensor]
     return torch.stack(cols, dim=-1)
 
 
+# ---- colour (the tracker's photometric term, reference system/tracker.py:131-172) -------------------------------------------------------
+# (frequency vector in cycles per metre, phase in cycles) of the waves of `texture`
+_TEXTURE_WAVES = [((0.9, 0.3, 0.5), 0.00), ((-0.4, 1.1, 0.6), 0.21), ((0.7, -0.8, 1.3), 0.47), ((1.9, 1.4, -1.1), 0.63), ((-2.3, 0.9, 2.1), 0.85)]
+_TEXTURE_AMP = [0.30, 0.25, 0.20, 0.15, 0.10]
+
+
+def _wave(x: torch.Tensor) -> torch.Tensor:
+    """A sinusoid of period 1 as two parabolas, 4 g (1 - |g|) with g = 2 frac(x) - 1: C1, in [-1, 1], and made of correctly rounded operations
+    only, so that — unlike sin — it has the same bits on every device and library."""
+    g = 2.0 * (x - torch.floor(x)) - 1.0
+    return 4.0 * g * (1.0 - torch.abs(g))
+
+
+def texture(p_world: torch.Tensor) -> torch.Tensor:
+    """A smooth colour for every world point: (..., 3) float -> (..., 3) float32 in [0, 1].  A fixed sum of five waves of the point, with another
+    phase per channel: two views of one surface point see one colour.  Evaluated in float64."""
+    p = p_world.to(torch.float64)
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    out = []
+    for ch in range(3):
+        acc = torch.zeros_like(x)
+        for ((fx, fy, fz), ph), amp in zip(_TEXTURE_WAVES, _TEXTURE_AMP):
+            acc = acc + amp * _wave(((fx * x + fy * y) + fz * z) + (ph + 0.31 * ch))
+        out.append(0.5 + 0.5 * acc)
+    return torch.stack(out, dim=-1).clamp(0.0, 1.0).to(torch.float32)
+
+
+def render_rgbd(scene: Scene, R: np.ndarray, t: np.ndarray, intr: Intrinsic, device: torch.device = torch.device("cpu"),
+                depth_cut: Tuple[float, float] = (0.5, 5.0), noise_seed: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One RGB-D frame: (rgb (H, W, 3) float32 in [0, 1], depth (H, W) float32 as `render_frame` gives it, noise and cut included).
+    The colour of a pixel is `texture` at its world hit point R (ray * depth) + t in float64, taken from the exact, uncut depth: every pixel
+    has a colour, whatever the depth sensor made of it."""
+    depth, _ = render_frame(scene, R, t, intr, device, depth_cut, noise_seed)
+    exact, _ = render_frame(scene, R, t, intr, device, (0.0, float("inf")), None)
+    H, W = intr.height, intr.width
+    f64 = torch.float64
+    u = torch.arange(W, device=device, dtype=f64)
+    v = torch.arange(H, device=device, dtype=f64)
+    s = exact.to(f64)
+    cx_ = ((u - intr.cx) / intr.fx).unsqueeze(0).expand(H, W) * s
+    cy_ = ((v - intr.cy) / intr.fy).unsqueeze(1).expand(H, W) * s
+    cols = [((float(R[r, 0]) * cx_ + float(R[r, 1]) * cy_) + float(R[r, 2]) * s) + float(t[r]) for r in range(3)]
+    return texture(torch.stack(cols, dim=-1)).contiguous(), depth
+
+
 @dataclass
 class MapConfig:
     """`args.mapping` keys of `pytorch/configs/fusion-lr-kt.yaml:27-35`."""

@@ -204,3 +204,84 @@ def estimate_normals(input_pc: torch.Tensor, max_nn: int, radius: float, cam_xyz
         _lib.check(_lib.load().dif_estimate_normals(_lib.ptr(input_pc), n, stride, int(max_nn), float(radius), cam, _lib.ptr(out), _lib.ptr(ws),
                                                     ws.numel(), _lib.stream_ptr()), "dif_estimate_normals")
     return out
+
+
+# ---- ext/imgproc/photometric.cu: the image kernels of the tracker's photometric term (tracker.py:41-56, 131-145) -----------------------
+def _image(t: torch.Tensor, what: str, last=None):
+    _lib.require_cuda(t)
+    if t.dtype != torch.float32 or t.dim() != (2 if last is None else 3) or (last is not None and t.size(2) != last):
+        raise RuntimeError(f"{what} must be a float32 (H,W{'' if last is None else ',' + str(last)}) tensor")
+    return t
+
+
+def gradient_xy(cur_intensity: torch.Tensor) -> torch.Tensor:
+    """(H,W) f32 -> (H,W,2) f32 Sobel gradient (dI/du, dI/dv), NaN on the one-pixel border.  reference `ext/imgproc/photometric.cu:3-22, 79-93`."""
+    _image(cur_intensity, "cur_intensity")
+    H, W = cur_intensity.shape
+    out = torch.empty((H, W, 2), dtype=torch.float32, device=cur_intensity.device)
+    with _dev(cur_intensity):
+        _lib.check(_lib.load().dif_gradient_xy(_lib.ptr(cur_intensity), H, W, _lib.ptr(out), _lib.stream_ptr()), "dif_gradient_xy")
+    return out
+
+
+def photo_args(intr, krkinv_data, kt_data, min_grad_scale: float, max_depth_delta: float, weight: float = 1.0, robust_kernel: int = 0,
+               robust_k: float = 0.0, no_grad: bool = False):
+    """`dif_rgb_hg_t` from the reference's argument lists (Python floats -> float32, like its `std::vector<float>` parameters)."""
+    a = _lib.DifRgbHg()
+    a.krkinv[:] = [float(x) for x in krkinv_data]
+    a.kt[:] = [float(x) for x in kt_data]
+    a.intr[:] = [float(x) for x in intr]
+    a.min_grad_scale, a.max_depth_delta, a.weight = float(min_grad_scale), float(max_depth_delta), float(weight)
+    a.robust_kernel, a.robust_k, a.no_grad = int(robust_kernel), float(robust_k), 1 if no_grad else 0
+    return a
+
+
+def rgb_odometry(prev_intensity: torch.Tensor, prev_depth: torch.Tensor, cur_intensity: torch.Tensor, cur_depth: torch.Tensor,
+                 cur_dIdxy: torch.Tensor, intr, krkinv_data, kt_data, min_grad_scale: float, max_depth_delta: float, compute_J: bool):
+    """[f (H,W)] or [f, J (H,W,6)]: the photometric residual of every pixel of the current frame against the previous frame under the warp
+    `krkinv_data` / `kt_data`, NaN where the pixel does not count, and its derivative (for -xi: the caller negates it).  reference
+    `ext/imgproc/photometric.cu:24-77, 95-138`; J is NaN where f is (the reference leaves those rows uninitialised)."""
+    import ctypes
+    for t, what in ((prev_intensity, "prev_intensity"), (prev_depth, "prev_depth"), (cur_intensity, "cur_intensity"), (cur_depth, "cur_depth")):
+        _image(t, what)
+        if t.shape != cur_intensity.shape:
+            raise RuntimeError("rgb_odometry: the four images must have one size")
+    _image(cur_dIdxy, "cur_dIdxy", 2)
+    H, W = cur_intensity.shape
+    if cur_dIdxy.shape[:2] != (H, W):
+        raise RuntimeError("rgb_odometry: cur_dIdxy must be (H,W,2)")
+    dev = cur_intensity.device
+    f = torch.empty((H, W), dtype=torch.float32, device=dev)
+    J = torch.empty((H, W, 6), dtype=torch.float32, device=dev) if compute_J else None
+    a = photo_args(intr, krkinv_data, kt_data, min_grad_scale, max_depth_delta)
+    with _dev(cur_intensity):
+        _lib.check(_lib.load().dif_rgb_odometry(_lib.ptr(prev_intensity), _lib.ptr(prev_depth), _lib.ptr(cur_intensity), _lib.ptr(cur_depth),
+                                                _lib.ptr(cur_dIdxy), H, W, ctypes.byref(a), _lib.ptr(f), _lib.ptr(J), _lib.stream_ptr()),
+                   "dif_rgb_odometry")
+    return [f, J] if compute_J else [f]
+
+
+def photo_pyramid(rgb: torch.Tensor, depth: torch.Tensor, intensity: torch.Tensor = None):
+    """The tracker's per-frame front end (tracker.py:83-85, 41-56) in three launches: ([I0, I1, I2], [D0, D1, D2], [G0, G1, G2]) with
+    I0 = mean of the three channels of `rgb` (H,W,3), level l + 1 = bilinear (intensity) / nearest (depth) resize of level l to half its size,
+    G = `gradient_xy` of I.  D0 is a copy of `depth`.  `rgb` None: `intensity` (H,W) is I0 itself."""
+    import ctypes
+    _image(depth, "depth")
+    H, W = depth.shape
+    if rgb is not None:
+        _image(rgb, "rgb", 3)
+    else:
+        _image(intensity, "intensity")
+    if (rgb if rgb is not None else intensity).shape[:2] != (H, W):
+        raise RuntimeError("photo_pyramid: colour / intensity and depth must have one size")
+    dev = depth.device
+    sizes = [(H, W), (H // 2, W // 2), (H // 2 // 2, W // 2 // 2)]
+    Is = [torch.empty(s, dtype=torch.float32, device=dev) if (l > 0 or rgb is not None) else intensity for l, s in enumerate(sizes)]
+    Ds = [torch.empty(s, dtype=torch.float32, device=dev) for s in sizes]
+    Gs = [torch.empty(s + (2,), dtype=torch.float32, device=dev) for s in sizes]
+    o = _lib.DifPhotoPyramid()
+    for l in range(3):
+        o.intensity[l], o.depth[l], o.gradient[l] = Is[l].data_ptr(), Ds[l].data_ptr(), Gs[l].data_ptr()
+    with _dev(depth):
+        _lib.check(_lib.load().dif_photo_pyramid(_lib.ptr(rgb), _lib.ptr(depth), H, W, ctypes.byref(o), _lib.stream_ptr()), "dif_photo_pyramid")
+    return Is, Ds, Gs

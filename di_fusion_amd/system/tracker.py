@@ -1,4 +1,4 @@
-"""The tracker's side of the map: the SDF term of `SDFTracker.gauss_newton` on libdifusion.so.
+"""The tracker: both terms of `SDFTracker.gauss_newton` on libdifusion.so.
 
 Reference: `pytorch/system/tracker.py`.  Its `compute_sdf_Hg` (tracker.py:174-218) is what calls `map.get_sdf` once per Gauss-Newton
 iteration — tens of times per frame, where the map is integrated once in twenty frames — and spreads the rest of the iteration over ~25
@@ -7,12 +7,17 @@ the decoder kernel over all points of the posed cloud — pose, validity test, l
 Jacobian, robust weights and the 6x6 / 6 / 1 sums in double in a fixed order) and the 44 numbers come back through pinned host memory,
 without a copy and without a stream synchronisation.
 
+The photometric term (`compute_rgb_Hg`, tracker.py:131-172) is one launch per evaluation (`dif_rgb_hg`: validity tests, warp, residual,
+Jacobian, robust weight and the same sums, no residual or Jacobian image in between) with the same hand-back; the image pyramid of a frame
+(tracker.py:41-56) is three launches (`dif_photo_pyramid`).  The reference passes the FULL-resolution intrinsics to every pyramid level
+(tracker.py:135-142), although levels 1 and 2 have half and a quarter of the pixels per axis; that is reproduced by default, and
+`rgb.level_calib = True` scales fx, fy, cx, cy by 0.5 ** level instead.
+
 What is here: `Pose` (the part of `utils.motion_util.Isometry` the loop needs, on plain rotation matrices: pyquaternion is not a
-dependency), `SDFTracker` with `compute_sdf_Hg`, `gauss_newton`, `track_camera` (the point-cloud preparation of tracker.py:87-118 on the HIP
-operators of `system.ext`).  What is not: the photometric term (`compute_rgb_Hg` needs the reference's `rgb_odometry` / `gradient_xy` image
-kernels, outside SURVEY.md section 8): `iter_config` entries naming 'rgb' raise NotImplementedError unless a subclass supplies
-`compute_rgb_Hg`.  A reference `SDFTracker` can use the fused term as it is: `compute_sdf_Hg` takes the reference's `Isometry` objects too
-(anything with `.q.rotation_matrix` and `.t`), see INTEGRATION.md.
+dependency), `sdf_hg` / `rgb_hg` (one evaluation of a term), `SDFTracker` with `compute_sdf_Hg`, `compute_rgb_Hg`, `_make_image_pyramid`,
+`gauss_newton`, `track_camera` (the point-cloud preparation of tracker.py:87-118 on the HIP operators of `system.ext`).  A reference
+`SDFTracker` can use the fused terms as they are: they take the reference's `Isometry` objects too (anything with `.q.rotation_matrix` and
+`.t`), and `system.ext` has `rgb_odometry` / `gradient_xy` with the reference's signatures, see INTEGRATION.md.
 """
 from __future__ import annotations
 
@@ -162,9 +167,59 @@ def sdf_hg(map_, obs_xyz: torch.Tensor, last_pose, cur_delta_pose, robust_kernel
     return r[:36].reshape(6, 6).copy(), r[36:42].copy(), float(r[42]), M
 
 
+def photo_warp(calib, cur_delta_pose, level_scale: float = 1.0):
+    """Host side of the photometric term (tracker.py:133-137, 142): (intr [fx, fy, cx, cy], K R K^-1 flattened, K t) in float64 — the Python
+    floats the reference hands to its kernel, which stores them as float32.  `level_scale` scales the intrinsics (`rgb.level_calib`)."""
+    p = Pose.of(cur_delta_pose)
+    intr = [float(calib.fx) * level_scale, float(calib.fy) * level_scale, float(calib.cx) * level_scale, float(calib.cy) * level_scale]
+    K = np.array([[intr[0], 0.0, intr[2]], [0.0, intr[1], intr[3]], [0.0, 0.0, 1.0]])
+    return intr, (K @ p.R @ np.linalg.inv(K)).flatten().tolist(), (K @ p.t).flatten().tolist()
+
+
+def rgb_hg(state_owner, prev_I: torch.Tensor, prev_D: torch.Tensor, cur_I: torch.Tensor, cur_D: torch.Tensor, cur_G: torch.Tensor, calib,
+           cur_delta_pose, weight: float = 1.0, robust_kernel=None, robust_k: float = 0.0, min_grad_scale: float = 0.0,
+           max_depth_delta: float = 0.0, no_grad: bool = False, level_scale: float = 1.0):
+    """The photometric term for one pose (reference tracker.py:131-172): (H (6,6) float64, g (6,) float64, sum_error float, M int), or
+    (None, None, sum_error, M) with `no_grad`; scaled by weight / M (M = 0: zeros).  Images: float32 on one GPU, (H,W) and (H,W,2).
+    `state_owner`: any object; the workspace and the pinned result slots are kept on it (`_rgb_hg_state`)."""
+    if robust_kernel not in ROBUST_KERNELS:
+        raise NotImplementedError(robust_kernel)
+    imgs = (prev_I, prev_D, cur_I, cur_D)
+    for t in imgs + (cur_G,):
+        _lib.require_cuda(t)
+        if t.dtype != torch.float32:
+            raise RuntimeError("rgb_hg: images must be float32")
+    H, W = cur_I.shape
+    if any(t.shape != (H, W) for t in imgs) or cur_G.shape != (H, W, 2):
+        raise RuntimeError("rgb_hg: the images of a level must have one size, the gradient (H,W,2)")
+    intr, krkinv, kt = photo_warp(calib, cur_delta_pose, level_scale)
+    a = ext.photo_args(intr, krkinv, kt, min_grad_scale, max_depth_delta, weight, ROBUST_KERNELS[robust_kernel], robust_k, no_grad)
+    lib = _lib.load()
+    dev = cur_I.device
+    st = getattr(state_owner, "_rgb_hg_state", None)
+    if st is None or st.dev != dev:
+        st = state_owner._rgb_hg_state = _HgState(dev)
+    with torch.cuda.device(dev):
+        if st.ws is None:
+            st.ws = torch.zeros((int(lib.dif_rgb_hg_workspace_bytes()) + 256,), dtype=torch.uint8, device=dev)      # (zero: the ticket's start)
+        off = (-st.ws.data_ptr()) % 256
+        st.seq += 1
+        k = st.seq & 3
+        _lib.check(lib.dif_rgb_hg(_lib.ptr(prev_I), _lib.ptr(prev_D), _lib.ptr(cur_I), _lib.ptr(cur_D), _lib.ptr(cur_G), H, W, ctypes.byref(a),
+                                  ctypes.c_void_p(st.ws.data_ptr() + off), st.ws.numel() - off, _lib.ptr(st.out), _lib.ptr(st.slots[k]), st.seq,
+                                  _lib.stream_ptr()), "dif_rgb_hg")
+        _lib.spin_until(st.words[k], 44, st.seq, "the tracker's photometric term")
+    r = st.slots_np[k]
+    M = int(r[43])
+    if no_grad:
+        return None, None, float(r[42]), M
+    return r[:36].reshape(6, 6).copy(), r[36:42].copy(), float(r[42]), M
+
+
 class SDFTracker:
-    """reference `system/tracker.py:26-283`, the SDF term on the fused path.  `args`: the reference's `tracking` block (a namespace or dict
-    with `sdf`, `rgb` (optional) and `iter_config`, configs/fusion-lr-kt.yaml:38-56)."""
+    """reference `system/tracker.py:26-283`, both terms on the fused path.  `args`: the reference's `tracking` block (a namespace or dict
+    with `sdf`, `rgb` (optional without 'rgb' terms) and `iter_config`, configs/fusion-lr-kt.yaml:38-56).  `rgb.level_calib` (not in the
+    reference, default False): scale the intrinsics of the photometric term with the pyramid level."""
 
     def __init__(self, map, args):
         self.map = map
@@ -188,9 +243,26 @@ class SDFTracker:
             raise ZeroDivisionError("no observation falls into a tracked voxel (tracker.py:209)")
         return H, g, e
 
-    def compute_rgb_Hg(self, pyramid_level, cur_delta_pose, cur_intensity_pyramid, cur_depth_pyramid, cur_dIdxy_pyramid, calib, no_grad=False):
-        raise NotImplementedError("the photometric term needs the reference's rgb_odometry / gradient_xy kernels (tracker.py:131-172), which are "
-                                  "outside the fusion path; use an iter_config of 'sdf' terms or override compute_rgb_Hg")
+    def _make_image_pyramid(self, intensity_img: torch.Tensor, depth_img: torch.Tensor):
+        """tracker.py:41-56: ([I0, I1, I2], [D0, D1, D2], [G0, G1, G2]) from the intensity image (I0 itself) and the depth image."""
+        return ext.photo_pyramid(None, depth_img, intensity_img)
+
+    def compute_rgb_Hg(self, pyramid_level: int, cur_delta_pose, cur_intensity_pyramid, cur_depth_pyramid, cur_dIdxy_pyramid, calib,
+                       no_grad: bool = False):
+        """tracker.py:131-172: (H, g, energy), H / g None with `no_grad`, against `last_intensity` / `last_depth`.  The intrinsics are the
+        full-resolution ones at every level, like the reference's, unless `rgb.level_calib` is set.  No valid pixel divides by zero there;
+        here too."""
+        if self.last_intensity is None or self.last_depth is None:
+            raise RuntimeError("compute_rgb_Hg needs the previous frame's pyramid (last_intensity / last_depth: track_camera keeps them)")
+        ra = self.rgb_args
+        lv = int(pyramid_level)
+        scale = 0.5 ** lv if getattr(ra, "level_calib", False) else 1.0
+        H, g, e, M = rgb_hg(self, self.last_intensity[lv], self.last_depth[lv], cur_intensity_pyramid[lv], cur_depth_pyramid[lv],
+                            cur_dIdxy_pyramid[lv], calib, cur_delta_pose, ra.weight, getattr(ra, "robust_kernel", None),
+                            getattr(ra, "robust_k", 0.0) or 0.0, ra.min_grad_scale, ra.max_depth_delta, no_grad, scale)
+        if M == 0:
+            raise ZeroDivisionError("no pixel of the current frame has a valid counterpart in the previous one (tracker.py:165)")
+        return H, g, e
 
     def _uses_rgb(self):
         return any(t[0] == "rgb" for grp in self.args.iter_config for t in grp["type"])
@@ -232,9 +304,15 @@ class SDFTracker:
     # -- per frame (tracker.py:74-129) -----------------------------------------------------------------------
     def track_camera(self, rgb_data, depth_data: torch.Tensor, calib, set_pose=None):
         """Point-cloud preparation of the frame (half-resolution unprojection, radius-outlier removal, PCA normals, 2 cm box filter: the
-        cloud `integrate_keyframe` takes, left in `last_processed_pc`), then the pose: `set_pose`, or Gauss-Newton from the previous one."""
+        cloud `integrate_keyframe` takes, left in `last_processed_pc`), then the pose: `set_pose`, or Gauss-Newton from the previous one.
+        With 'rgb' terms in `iter_config`, `rgb_data` (H,W,3) float32 is required: its pyramid is built, handed to the loop and kept in
+        `last_intensity` / `last_depth` for the next frame.  Without them `rgb_data` is not looked at.  `last_colored_pcd` (the reference's
+        texture storage, tracker.py:115) is not kept: it stays None."""
+        pyr = (None, None, None)
         if self._uses_rgb():
-            self.compute_rgb_Hg(None, None, None, None, None, calib)          # raises unless a subclass supplies the term and its pyramids
+            if rgb_data is None:
+                raise ValueError("iter_config names 'rgb' terms: track_camera needs rgb_data (H,W,3) float32, got None")
+            pyr = ext.photo_pyramid(rgb_data.contiguous(), depth_data.contiguous())
         sc = float(self.sdf_args.subsample)
         d = torch.nn.functional.interpolate(depth_data[None, None], scale_factor=sc, mode="nearest", recompute_scale_factor=False)[0, 0].contiguous()
         pc = ext.unproject_depth(d, calib.fx * sc, calib.fy * sc, calib.cx * sc, calib.cy * sc).reshape(-1, 3)
@@ -250,6 +328,8 @@ class SDFTracker:
             pose = Pose.of(set_pose)
         else:
             assert len(self.all_pd_pose) > 0
-            pose = self.gauss_newton(self.all_pd_pose[-1], None, None, None, pc, calib)
+            pose = self.gauss_newton(self.all_pd_pose[-1], pyr[0], pyr[1], pyr[2], pc, calib)
+        if pyr[0] is not None:
+            self.last_intensity, self.last_depth = pyr[0], pyr[1]
         self.all_pd_pose.append(pose)
         return pose

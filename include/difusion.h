@@ -456,6 +456,51 @@ int64_t dif_sdf_hg_workspace_bytes(int64_t N);
 int dif_sdf_hg(const dif_map_t* map, const dif_weights_t* w, const float* obs_xyz, int64_t N, const dif_sdf_hg_t* args, void* ws, int64_t ws_bytes,
                double* out, double* out_host, int64_t seq, void* stream);
 
+/* ---- the photometric term of the tracker's Gauss-Newton step (ext/imgproc/photometric.cu, tracker.py:41-56, 131-172) ----------------------------
+ * All images are row-major float32 on the device; v indexes rows, u columns. */
+/* Sobel gradient of an (H, W) intensity image: out (H, W, 2) = (dI/du, dI/dv), (d1 + 2 d2 + d3) / 8; the one-pixel border is NaN. */
+int dif_gradient_xy(const float* intensity, int32_t H, int32_t W, float* out, void* stream);
+/* The per-frame front end (tracker.py:83-85): intensity = mean of the three channels of rgb (H, W, 3); levels l = 0, 1, 2 of size
+ * (H >> l, W >> l) (floor at every step): intensity by bilinear and depth by nearest resizing of the level above (torch.nn.functional.interpolate,
+ * align_corners = False), gradient[l] = dif_gradient_xy(intensity[l]).  depth[0] is a copy of `depth`.  Three launches.  H, W >= 4.
+ * rgb == NULL: intensity[0] is an INPUT (the caller's intensity image, tracker.py:41 _make_image_pyramid). */
+typedef struct dif_photo_pyramid_t {
+    float* intensity[3];    /* (H >> l, W >> l)    */
+    float* depth[3];        /* (H >> l, W >> l)    */
+    float* gradient[3];     /* (H >> l, W >> l, 2) */
+} dif_photo_pyramid_t;
+int dif_photo_pyramid(const float* rgb, const float* depth, int32_t H, int32_t W, const dif_photo_pyramid_t* out, void* stream);
+/* One evaluation of the term for the pose cur_delta_pose = [R | t] (previous frame <- current frame).  A pixel (v, u) of the current frame
+ * counts if its squared gradient is not NaN and >= min_grad_scale, its depth d is not NaN, its warp target (u0, v0) = round-half-even of
+ * (d (K R K^-1 (u, v, 1)) + K t) / z lies inside the image, and the previous depth there is not NaN, > 0 and within max_depth_delta of the
+ * warped depth z.  A non-finite quotient (z == 0) rounds like CUDA's __float2int_rn: NaN -> 0, +-inf -> out of the image.
+ * intr = fx, fy, cx, cy: used for the Jacobian only.  robust_kernel / robust_k weigh the residual f (0 none, 1 huber, 2 tukey). */
+typedef struct dif_rgb_hg_t {
+    float krkinv[9];        /* K R K^-1, row-major (tracker.py:136)        */
+    float kt[3];            /* K t (tracker.py:137)                         */
+    float intr[4];          /* fx, fy, cx, cy                               */
+    float min_grad_scale;
+    float max_depth_delta;
+    float weight;           /* the term's weight (tracker.py:165); dif_rgb_hg only */
+    int32_t robust_kernel;  /* dif_rgb_hg only                              */
+    float robust_k;         /* dif_rgb_hg only                              */
+    int32_t no_grad;        /* dif_rgb_hg only                              */
+} dif_rgb_hg_t;
+/* The flat operator (the reference's rgb_odometry): f_out (H, W) = cur_I[v][u] - prev_I[v0][u0], NaN where the pixel does not count;
+ * J_out (H, W, 6), optional (NULL: not computed) = d f / d xi as the reference's kernel writes it (its caller negates it), NaN where f is. */
+int dif_rgb_odometry(const float* prev_I, const float* prev_D, const float* cur_I, const float* cur_D, const float* cur_G, int32_t H, int32_t W,
+                     const dif_rgb_hg_t* args, float* f_out, float* J_out, void* stream);
+/* The whole term in ONE launch, nothing per pixel stored: with J = -(the flat operator's), w = robust(f) and s = 1 / M * weight over the M pixels
+ * that count, H = s sum (J w) (x) J, g = s sum J (f w), sum_error = s sum f (f w) (tracker.py:152-172).  Per-pixel quantities are float32 exactly
+ * as dif_rgb_odometry computes them, products and sums are double in a fixed order: the same inputs give the same bits.
+ * out / out_host / seq: as dif_sdf_hg (H [0,36), g [36,42), sum_error [42], M [43]; M = 0 -> all zero).  no_grad != 0: sum_error and M only.
+ * ws: dif_rgb_hg_workspace_bytes() bytes of device memory, 256-byte aligned, ZERO when first used (every call leaves it ready for the next),
+ * private to the call's stream while it runs.  DIF_EINVAL (nothing launched): a short or misaligned workspace, an unknown robust kernel, a missing
+ * image or result pointer, H < 3 or W < 3. */
+int64_t dif_rgb_hg_workspace_bytes(void);
+int dif_rgb_hg(const float* prev_I, const float* prev_D, const float* cur_I, const float* cur_D, const float* cur_G, int32_t H, int32_t W,
+               const dif_rgb_hg_t* args, void* ws, int64_t ws_bytes, double* out, double* out_host, int64_t seq, void* stream);
+
 /* ---- multi-GPU map merge (no reference counterpart) ----------------------------------- */
 /* Pack the allocated voxels whose x index lies in [x_lo, x_hi) as 32-word records, in slot order:
  *   lin int32 | flags int32 (bit 0 = dirty) | w f32 | payload f32[29],  payload = w*z (raw == 0: additive merge) or z itself (raw != 0: exact copy).
