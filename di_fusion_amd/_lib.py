@@ -90,6 +90,13 @@ class DifRgbHg(ctypes.Structure):
                 ("weight", c_float), ("robust_kernel", c_int32), ("robust_k", c_float), ("no_grad", c_int32)]
 
 
+class DifWeldArgs(ctypes.Structure):
+    """include/difusion.h: dif_weld_args_t"""
+    _fields_ = [("bound_min", c_float * 3), ("voxel_size", c_float), ("resolution", c_int32), ("n_xyz", c_int32 * 3)]
+
+
+WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 0, 1, 2, 3, 4, 8       # DIF_WELD_*
+
 SIGNATURES = {
     "dif_version": (c_int32, []),
     "dif_build_id": (ctypes.c_char_p, []),
@@ -129,6 +136,9 @@ SIGNATURES = {
     "dif_mesh_cache_export_dma": (c_int32, [POINTER(DifExtractBuffers), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_mesh_cache_compact": (c_int32, [POINTER(DifMap), POINTER(DifExtractBuffers), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "dif_mesh_cache_reindex": (c_int32, [POINTER(DifMap), POINTER(DifExtractBuffers), c_int64, c_void_p]),
+    "dif_mesh_weld_workspace_bytes": (c_int64, [c_int64]),
+    "dif_mesh_weld": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DifWeldArgs), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
     "dif_marching_cubes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_int32, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),

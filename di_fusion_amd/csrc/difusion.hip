@@ -133,6 +133,7 @@ inline int grid_for(int64_t n, int per_block = DIF_BLOCK, int max_blocks = 4096)
 #include "kernels_extract.hip.h"
 #include "kernels_mesh.hip.h"
 #include "kernels_cloud.hip.h"
+#include "kernels_weld.hip.h"
 #include "kernels_optimize.hip.h"
 #include "kernels_track.hip.h"
 #include "kernels_photo.hip.h"
@@ -1617,6 +1618,83 @@ int dif_mesh_cache_reindex(const dif_map_t* map, const dif_extract_buffers_t* bu
     if (hipMemsetAsync(map->tri_n, 0, sizeof(int32_t) * (size_t)map->capacity, s) != hipSuccess) return DIF_ELAUNCH;
     hipLaunchKernelGGL(k_cache_reindex, dim3(grid_for(n > 0 ? n : 1)), dim3(DIF_BLOCK), 0, s, (const int64_t*)buf->cache_id, n, (const int64_t*)map->indexer,
                        map->tri_start, map->tri_n, buf->cache_alive, map->counters);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- indexed mesh ------------------------------------------------------------------------------------------------
+extern "C++" {
+struct WeldWs {
+    WeldTable t;
+    int* slot;              // [3T]  table slot of a corner, negative: own vertex
+    int* corner_vertex;     // [3T]
+    long long* nsum;        // [3T][3] fixed-point normal sums (cleared per vertex by the vertex scan)
+    int* block_tmp;         // [4096]
+    size_t clear_bytes;     // keys and minima are adjacent: one all-ones fill
+    int64_t total_bytes;
+};
+
+static int carve_weld(int64_t T, void* base, WeldWs& ws) {
+    if (T < 0 || 3 * T >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    int64_t cap = 64;
+    int bits = 6;
+    while (cap < 6 * T) { cap <<= 1; ++bits; }           // twice the corners: never more than half full
+    const size_t n = (size_t)(T > 0 ? 3 * T : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_key = take((size_t)cap * 8), o_min = take((size_t)cap * 4), o_vertex = take((size_t)cap * 4);
+    const size_t o_slot = take(n * 4), o_cv = take(n * 4), o_nsum = take(n * 3 * 8), o_tmp = take(4096 * 4);
+    ws.clear_bytes = o_vertex - o_key;
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.t.key = (unsigned long long*)(b + o_key);
+        ws.t.min_corner = (unsigned*)(b + o_min);
+        ws.t.vertex = (int*)(b + o_vertex);
+        ws.t.mask = (unsigned)(cap - 1);
+        ws.t.shift = 64 - bits;
+        ws.slot = (int*)(b + o_slot);
+        ws.corner_vertex = (int*)(b + o_cv);
+        ws.nsum = (long long*)(b + o_nsum);
+        ws.block_tmp = (int*)(b + o_tmp);
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_weld_workspace_bytes(int64_t T) {
+    WeldWs ws;
+    if (carve_weld(T, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_weld(const float* tri, const float* tri_std, const int64_t* tri_id, int64_t T, const dif_weld_args_t* args, void* workspace,
+                  int64_t workspace_bytes, float* vertices, float* normals, float* vertex_std, int32_t* triangles, int64_t* triangle_id,
+                  int32_t* counts, void* stream) {
+    if (!args || !counts || T < 0 || 3 * T >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    if (!(args->voxel_size > 0.0f) || args->resolution < 1 || args->resolution >= (1 << 20)) return DIF_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (args->n_xyz[k] < 0 || (int64_t)args->n_xyz[k] * args->resolution + 1 >= ((int64_t)1 << 20)) return DIF_EINVAL;     // the key has 20 bits per axis
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_WELD_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (T == 0) return DIF_OK;
+    if (!tri || !tri_std || !tri_id || !workspace || !vertices || !normals || !vertex_std || !triangles || !triangle_id) return DIF_EINVAL;
+    WeldWs ws;
+    if (carve_weld(T, workspace, ws) != DIF_OK) return DIF_EINVAL;
+    if (ws.total_bytes > workspace_bytes) return DIF_ENOSPACE;
+    const int n = (int)(3 * T);
+    const dim3 corners((unsigned)((n + DIF_BLOCK - 1) / DIF_BLOCK)), block(DIF_BLOCK);
+    const WeldGeo g{args->bound_min[0], args->bound_min[1], args->bound_min[2], args->voxel_size, (float)args->resolution};
+    if (hipMemsetAsync(ws.t.key, 0xFF, ws.clear_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_weld_insert, corners, block, 0, s, ws.t, g, tri, n, ws.slot, counts);
+    DIF_CHECK_LAUNCH();
+    WeldVertexFunctor fv{ws.t, ws.slot, tri, tri_std, vertices, vertex_std, ws.nsum, counts};
+    if (launch_scan(fv, nullptr, n, n, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_weld_triangles, corners, block, 0, s, ws.t, (const int*)ws.slot, n, ws.corner_vertex);
+    DIF_CHECK_LAUNCH();
+    WeldTriangleFunctor ft{ws.corner_vertex, tri_id, vertices, triangles, triangle_id, ws.nsum, (float)args->resolution / args->voxel_size, (int)T, counts};
+    if (launch_scan(ft, nullptr, (int)T, T, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_weld_normals, corners, block, 0, s, (const long long*)ws.nsum, (const int*)counts, normals);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

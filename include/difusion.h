@@ -398,6 +398,33 @@ int dif_mesh_cache_compact(const dif_map_t* map, const dif_extract_buffers_t* bu
  * alive, set CACHE_T = CACHE_KEPT = n, CACHE_DEAD = 0. */
 int dif_mesh_cache_reindex(const dif_map_t* map, const dif_extract_buffers_t* buf, int64_t n, void* stream);
 
+/* ---- indexed mesh: weld the triangle soup by lattice edge, vertex normals (no reference counterpart; DESIGN.md "Indexed mesh") ---------- */
+/* The soup (mesh-cache arrays: tri (T,3,3) world positions, tri_std (T,3), tri_id (T)) -> one vertex per LATTICE EDGE that carries soup corners.
+ * Key of a corner, all float32: per axis L = ((p - bound_min) / voxel_size) * resolution, q = rintf(L), f = |L - q|; a = the axis with the largest
+ * f (ties: lowest).  Either other f >= 2^-10: the corner is not on the lattice — UNKEYED: a vertex of its own, welded to nothing, counted.
+ * f[a] < 2^-10: key (q, 3), a lattice corner; else key (q with floorf(L[a]) on axis a, a).  A coordinate outside [0, 2^20): unkeyed.
+ * A class's vertex is its lowest soup corner (position and std copied, not averaged); vertices come in the soup order of those corners,
+ * triangles in soup order without those that repeat an index, the voxel id with its triangle: the output does not depend on scheduling.
+ * Normals: area-weighted; per kept triangle the float32 cross product of its edges in lattice units, each component as llrint(c * 2^30) added
+ * to the three vertices' int64 sums, normalised in double; a vertex without a kept triangle gets (0,0,0).
+ * counts (int32[DIF_WELD_COUNT], device): DIF_WELD_* below.  Outputs are sized for the worst case (no two corners weld); rows beyond the
+ * counts are not written. */
+typedef struct dif_weld_args {
+    float bound_min[3];
+    float voxel_size;
+    int32_t resolution;     /* of the extract that produced the soup */
+    int32_t n_xyz[3];       /* the map's voxel grid, or zeros: a grid with n * resolution + 1 >= 2^20 on an axis is refused (DIF_EINVAL) */
+} dif_weld_args_t;
+enum { DIF_WELD_VERTICES = 0, DIF_WELD_KEPT = 1, DIF_WELD_DROPPED = 2, DIF_WELD_UNKEYED = 3,
+       DIF_WELD_STATUS = 4 /* 0, or 1: the class table overflowed (cannot happen: it holds twice the corners; reported instead of looping) */,
+       DIF_WELD_COUNT = 8 };
+/* Bytes of workspace for T triangles (-1: T < 0 or 3 T >= 2^31). */
+int64_t dif_mesh_weld_workspace_bytes(int64_t T);
+/* T = 0 is valid (counts all zero).  vertices, normals (3T,3) f32; vertex_std (3T) f32; triangles (T,3) i32; triangle_id (T) i64. */
+int dif_mesh_weld(const float* tri, const float* tri_std, const int64_t* tri_id, int64_t T, const dif_weld_args_t* args, void* workspace,
+                  int64_t workspace_bytes, float* vertices, float* normals, float* vertex_std, int32_t* triangles, int64_t* triangle_id,
+                  int32_t* counts, void* stream);
+
 /* Flat marching cubes = ext/marching_cubes mc.cpp:3-16.  indexer (nx,ny,nz) i64, valid_blocks (K) i64,
  * vec_batch_mapping (V) i32, cube_sdf/std (B,R,R,R) f32.  counters[DIF_C_T] receives the triangle count.      */
 int dif_marching_cubes(const int64_t* indexer, int32_t nx, int32_t ny, int32_t nz, const int64_t* valid_blocks,
