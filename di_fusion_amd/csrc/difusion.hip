@@ -118,12 +118,27 @@ inline int wait_word(hipStream_t s, uint32_t* word, int32_t value) {
     return hipStreamWaitValue32(s, word, (uint32_t)value, hipStreamWaitValueGte, 0xFFFFFFFFu) == hipSuccess ? DIF_OK : DIF_ELAUNCH;
 }
 
+// which blobs a weight set carries (include/difusion.h: dif_weights_t; caller-owned, so asked per call).  Every launch site names the blobs ITS
+// kernels read: the fused lattice chain asks for dec_x6 without dec_x6u, because k_decode_voxels<true> and k_decode_refine_x6 never read the
+// unfolded-input blob, while launch_decode's bf16-pipe kernels read both (and the gradient kernels dec_x6b as well).
+inline bool has_enc(const dif_weights_t* w) { return w->enc_packed && w->enc_packed_floats == ENC_FLOATS; }
+inline bool has_enc_x6(const dif_weights_t* w) { return w->enc_x6_packed && w->enc_x6_packed_bytes == E6_BYTES; }
+inline bool has_dec(const dif_weights_t* w) { return w->dec_packed && w->dec_packed_floats == DEC_FLOATS; }
+inline bool has_dec_bwd(const dif_weights_t* w) { return w->dec_bwd_packed && w->dec_bwd_packed_floats == DECB_FLOATS; }
+inline bool has_dec_fold(const dif_weights_t* w) { return w->dec_fold_packed && w->dec_fold_packed_floats == DECF_FLOATS; }
+inline bool has_dec_x6(const dif_weights_t* w) { return w->dec_x6_packed && w->dec_x6_packed_bytes == X6_BYTES; }
+inline bool has_dec_x6u(const dif_weights_t* w) { return w->dec_x6u_packed && w->dec_x6u_packed_bytes == X6U_BYTES; }
+inline bool has_dec_x6b(const dif_weights_t* w) { return w->dec_x6b_packed && w->dec_x6b_packed_bytes == X6B_BYTES; }
+
 inline int grid_for(int64_t n, int per_block = DIF_BLOCK, int max_blocks = 4096) {
     int64_t b = (n + per_block - 1) / per_block;
     if (b < 1) b = 1;
     if (b > max_blocks) b = max_blocks;
     return (int)b;
 }
+// persistent kernels (MLP tiles, lattice voxels): one workgroup per `per_block` items, at most one per CU.  (Two callers — the voxel lattice and
+// dif_encode_rows — used to leave the lower clamp out: their item counts are >= 1.)
+inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_block, num_cus()); }
 
 #ifndef GRAD_X6_PF
 #define GRAD_X6_PF 3          /* weight steps (3 KB each) a wave keeps in flight in the gradient kernels (3, 6 and 10 measured the same) */
@@ -437,11 +452,15 @@ struct FrameSource {            // integrate straight from a depth frame: the fi
 struct IntegratePlan {
     UvcArgs uvc; PruneArgs prune; AllocFunctor alloc; const int* alloc_tot; GatherArgs gather; EncArgs enc; FuseArgs fuse;
     int64_t grid; bool has_pending; bool overlap;
+    // launch shapes: workgroups of the three point passes; k_focus_gather's image width (it walks 16x16 pixel tiles of a frame whose sides allow
+    // it) or 0; the encoder's tiles on the bf16 matrix pipe (mlp.hip.h) or the f32-input MFMA, and its LDS bytes; k_fuse's grid
+    int nb_pts, gather_img_w; bool enc_x6; size_t enc_lds; int fuse_grid;
 };
 
 static int integrate_plan(const dif_map_t* map, const dif_weights_t* w, const float* xyz, const float* normal, int64_t N, uint8_t* unq_mask,
                           void* wsp, int64_t ws_bytes, const FrameSource* src, IntegratePlan& P) {
-    if (!map || !w || !w->enc_packed || w->enc_packed_floats != ENC_FLOATS || N <= 0 || !map->grid_tot) return DIF_EINVAL;
+    if (!map || !w || !has_enc(w) || N < 0 || !map->grid_tot) return DIF_EINVAL;
+    if (N == 0) return DIF_OK;          // an empty cloud: nothing else is looked at, P stays unset and the caller launches nothing
     // a streaming frame may leave xyz / normal out (both): the later stages then recompute the few points they need from the depth pixel
     if ((xyz == nullptr) != (normal == nullptr) || (!xyz && !src) || !unq_mask || !wsp) return DIF_EINVAL;
     if (8 * N + 64 >= (int64_t)1 << 31 || map->capacity >= (int64_t)1 << 31) return DIF_EINVAL;      // record ids and slots are int32
@@ -478,6 +497,11 @@ static int integrate_plan(const dif_map_t* map, const dif_weights_t* w, const fl
     P.fuse = FuseArgs{ws.rec, ws.rec_next, map->rec_dir, map->upd_list, map->latent_vecs, map->voxel_obs_count, map->dirty, C, map->latent_vecs_pos,
                       halo_lists_of(map), ov ? nullptr : pending, ov ? map->dirty_tot : nullptr, ov ? map->frame_counters : nullptr};
     if (ov) P.uvc.pending = nullptr;                               // (no deferred export rides with an overlapped frame: its extract has not run yet)
+    P.nb_pts = (int)((N + DIF_BLOCK - 1) / DIF_BLOCK);
+    P.gather_img_w = (src && src->W % 16 == 0 && src->H % 16 == 0) ? src->W : 0;
+    P.enc_x6 = has_enc_x6(w);
+    P.enc_lds = P.enc_x6 ? (size_t)E6_BYTES : (size_t)ENC_FLOATS * 4;
+    P.fuse_grid = grid_for(map->capacity * 32, DIF_BLOCK, 256);
     return DIF_OK;
 }
 
@@ -507,15 +531,11 @@ static int encoder_attributes() {
 
 static int integrate_impl(const dif_map_t* map, const dif_weights_t* w, const float* xyz, const float* normal, int64_t N, uint8_t* unq_mask,
                           void* wsp, int64_t ws_bytes, const FrameSource* src, void* stream_) {
-    if (!map || !w || !w->enc_packed || w->enc_packed_floats != ENC_FLOATS || N < 0 || !map->grid_tot) return DIF_EINVAL;
-    if (N == 0) return DIF_OK;
-    if (!src && (!xyz || !normal)) return DIF_EINVAL;
     IntegratePlan P;
     const int rc = integrate_plan(map, w, xyz, normal, N, unq_mask, wsp, ws_bytes, src, P);
-    if (rc != DIF_OK) return rc;
+    if (rc != DIF_OK || N == 0) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    const int nb_pts = (int)((N + DIF_BLOCK - 1) / DIF_BLOCK);
-    const int nb_x = P.has_pending ? DIF_EXPORT_WGS : 0;
+    const int nb_pts = P.nb_pts, nb_x = P.has_pending ? DIF_EXPORT_WGS : 0;
     // two queues: the front end reads what the previous frame's fusion kernel (extracts' stream) wrote; that frame's extract says when it is done
     if (P.overlap && wait_word(s, map->sync_words + DIF_SYNC_FUSED, map->frame_seq - 1) != DIF_OK) return DIF_ELAUNCH;
     // k_voxel_count also zeroes the per-call counters (ALLOC_NEW, M, C, ITEMS): every kernel that writes them runs later
@@ -527,11 +547,9 @@ static int integrate_impl(const dif_map_t* map, const dif_weights_t* w, const fl
     hipLaunchKernelGGL(k_prune_mark, dim3(nb_pts + nb_x), dim3(DIF_BLOCK), 0, s, P.prune, N, nb_x);
     DIF_CHECK_LAUNCH();
     if (launch_counted_scan(P.alloc, (int)((P.grid + 31) / 32), P.alloc_tot, s) != DIF_OK) return DIF_ELAUNCH;
-    hipLaunchKernelGGL(k_focus_gather, dim3(nb_pts + nb_x), dim3(DIF_BLOCK), 0, s, P.gather, N, (src && src->W % 16 == 0 && src->H % 16 == 0) ? src->W : 0, nb_x);
+    hipLaunchKernelGGL(k_focus_gather, dim3(nb_pts + nb_x), dim3(DIF_BLOCK), 0, s, P.gather, N, P.gather_img_w, nb_x);
     DIF_CHECK_LAUNCH();
     {
-        const bool x6 = w->enc_x6_packed && w->enc_x6_packed_bytes == E6_BYTES;          // tiles on the bf16 matrix pipe (mlp.hip.h)
-        const size_t lds_bytes = x6 ? (size_t)E6_BYTES : (size_t)ENC_FLOATS * 4;
         if (encoder_attributes() != DIF_OK) return DIF_ELAUNCH;
         const EncArgs& e = P.enc;
         ProfScope prof(DIF_PROF_ENCODE, s);
@@ -540,11 +558,11 @@ static int integrate_impl(const dif_map_t* map, const dif_weights_t* w, const fl
         // 96: 6,370, 64: 5,990, 32: 4,930 (it becomes the critical path: 74 us on 64 CUs), and the decode kernels take their 43-45 us beside ANY of
         // them — so it keeps all CUs.
         const int enc_grid = P.overlap ? overlap_encoder_cus() : num_cus();
-        if (x6)
-            hipLaunchKernelGGL(k_encode<true>, dim3(enc_grid), dim3(ENC_X6_THREADS), lds_bytes, s, e.g, (const float*)w->enc_x6_packed, e.src.xyz, e.src.normal, e.src.frame,
+        if (P.enc_x6)
+            hipLaunchKernelGGL(k_encode<true>, dim3(enc_grid), dim3(ENC_X6_THREADS), P.enc_lds, s, e.g, (const float*)w->enc_x6_packed, e.src.xyz, e.src.normal, e.src.frame,
                                e.src.im, N, e.pair_list, e.rec_dir, e.rec_next, e.rec, e.upd_list, e.counters, e.dirty, e.dirty_tot);
         else
-            hipLaunchKernelGGL(k_encode<false>, dim3(enc_grid), dim3(512), lds_bytes, s, e.g, w->enc_packed, e.src.xyz, e.src.normal, e.src.frame,
+            hipLaunchKernelGGL(k_encode<false>, dim3(enc_grid), dim3(512), P.enc_lds, s, e.g, w->enc_packed, e.src.xyz, e.src.normal, e.src.frame,
                                e.src.im, N, e.pair_list, e.rec_dir, e.rec_next, e.rec, e.upd_list, e.counters, e.dirty, e.dirty_tot);
         DIF_CHECK_LAUNCH();
     }
@@ -556,7 +574,7 @@ static int integrate_impl(const dif_map_t* map, const dif_weights_t* w, const fl
         hipLaunchKernelGGL(k_publish_word, dim3(1), dim3(64), 0, s, map->sync_words + DIF_SYNC_FRONT_DONE, (uint32_t)map->frame_seq);
         if (wait_word(sf, map->sync_words + DIF_SYNC_FRONT_DONE, map->frame_seq) != DIF_OK) return DIF_ELAUNCH;
     }
-    hipLaunchKernelGGL(k_fuse, dim3(grid_for(map->capacity * 32, DIF_BLOCK, 256)), dim3(DIF_BLOCK), 0, sf, P.fuse);
+    hipLaunchKernelGGL(k_fuse, dim3(P.fuse_grid), dim3(DIF_BLOCK), 0, sf, P.fuse);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
@@ -589,43 +607,38 @@ static bool batch_maps_ok(const dif_stream_frame_t* st, int S) {
 
 int dif_integrate_frames(const dif_stream_frame_t* st, int32_t S, const dif_weights_t* w, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
                          void* stream_) {
-    if (!batch_maps_ok(st, S) || !w || H <= 0 || W <= 0) return DIF_EINVAL;
-    const bool x6 = w->enc_x6_packed && w->enc_x6_packed_bytes == E6_BYTES;
-    if (!w->enc_packed || w->enc_packed_floats != ENC_FLOATS) return DIF_EINVAL;
+    if (!batch_maps_ok(st, S) || !w || H <= 0 || W <= 0 || !has_enc(w)) return DIF_EINVAL;
     const int64_t N = (int64_t)H * W;
     static thread_local Batch<UvcArgs> uvc; static thread_local Batch<PruneArgs> prune; static thread_local ScanBatch<AllocFunctor> alloc;
     static thread_local Batch<GatherArgs> gather; static thread_local Batch<EncArgs> enc; static thread_local Batch<FuseArgs> fuse;
-    int64_t grid = 0;
+    IntegratePlan P;          // (what is left in it after the loop — the shapes — is the same for every map: one N, one capacity, one grid)
     for (int j = 0; j < S; ++j) {
         if (!st[j].frame_dev) return DIF_EINVAL;
         FrameSource src{st[j].frame_dev, H, W, fx, fy, cx, cy};
-        IntegratePlan P;
         const int rc = integrate_plan(st[j].map, w, st[j].xyz_world, st[j].normal_world, N, st[j].unq_mask, st[j].ws, st[j].ws_bytes, &src, P);
         if (rc != DIF_OK) return rc;
         uvc.s[j] = P.uvc; prune.s[j] = P.prune; alloc.f[j] = P.alloc; alloc.tot[j] = P.alloc_tot; gather.s[j] = P.gather; enc.s[j] = P.enc; fuse.s[j] = P.fuse;
-        grid = P.grid;
     }
     for (int j = S; j < DIF_MAX_STREAMS; ++j) {          // unused entries: never dereferenced, but never garbage either
         uvc.s[j] = uvc.s[0]; prune.s[j] = prune.s[0]; alloc.f[j] = alloc.f[0]; alloc.tot[j] = alloc.tot[0]; gather.s[j] = gather.s[0]; enc.s[j] = enc.s[0];
         fuse.s[j] = fuse.s[0];
     }
     hipStream_t s = (hipStream_t)stream_;
-    const int nb_pts = (int)((N + DIF_BLOCK - 1) / DIF_BLOCK), nb_x = DIF_EXPORT_WGS;
+    const int nb_pts = P.nb_pts, nb_x = DIF_EXPORT_WGS;
     hipLaunchKernelGGL(k_unproject_voxel_count_batch, dim3(nb_pts + nb_x, S), dim3(DIF_BLOCK), 0, s, uvc, ImageGeo{H, W, fx, fy, cx, cy}, nb_x);
     hipLaunchKernelGGL(k_prune_mark_batch, dim3(nb_pts + nb_x, S), dim3(DIF_BLOCK), 0, s, prune, N, nb_x);
     DIF_CHECK_LAUNCH();
-    if (launch_counted_scan_batch(alloc, S, (int)((grid + 31) / 32), s) != DIF_OK) return DIF_ELAUNCH;
-    hipLaunchKernelGGL(k_focus_gather_batch, dim3(nb_pts + nb_x, S), dim3(DIF_BLOCK), 0, s, gather, N, (W % 16 == 0 && H % 16 == 0) ? W : 0, nb_x);
+    if (launch_counted_scan_batch(alloc, S, (int)((P.grid + 31) / 32), s) != DIF_OK) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_focus_gather_batch, dim3(nb_pts + nb_x, S), dim3(DIF_BLOCK), 0, s, gather, N, P.gather_img_w, nb_x);
     DIF_CHECK_LAUNCH();
     {
-        const size_t lds_bytes = x6 ? (size_t)E6_BYTES : (size_t)ENC_FLOATS * 4;
         if (encoder_attributes() != DIF_OK) return DIF_ELAUNCH;
         ProfScope prof(DIF_PROF_ENCODE, s);
-        if (x6) hipLaunchKernelGGL(k_encode_batch<true>, dim3(num_cus()), dim3(ENC_X6_THREADS), lds_bytes, s, enc, (int)S, (const float*)w->enc_x6_packed, N);
-        else hipLaunchKernelGGL(k_encode_batch<false>, dim3(num_cus()), dim3(512), lds_bytes, s, enc, (int)S, w->enc_packed, N);
+        if (P.enc_x6) hipLaunchKernelGGL(k_encode_batch<true>, dim3(num_cus()), dim3(ENC_X6_THREADS), P.enc_lds, s, enc, (int)S, (const float*)w->enc_x6_packed, N);
+        else hipLaunchKernelGGL(k_encode_batch<false>, dim3(num_cus()), dim3(512), P.enc_lds, s, enc, (int)S, w->enc_packed, N);
         DIF_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_fuse_batch, dim3(grid_for(st[0].map->capacity * 32, DIF_BLOCK, 256), S), dim3(DIF_BLOCK), 0, s, fuse);
+    hipLaunchKernelGGL(k_fuse_batch, dim3(P.fuse_grid, S), dim3(DIF_BLOCK), 0, s, fuse);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
@@ -667,7 +680,7 @@ int64_t dif_optimize_workspace_bytes(int64_t N, int64_t capacity) {
 int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const float* xyz, const float* normal, int64_t N, const uint8_t* unq_mask,
                          const float* noise, int32_t n_iters, float lr, float code_reg_lambda, float* loss_out, void* wsp, int64_t ws_bytes, void* stream_) {
     if (!map || !w || !map->voxel_optimized || N < 0 || n_iters < 0 || !(lr > 0.0f) || code_reg_lambda < 0.0f) return DIF_EINVAL;
-    if (!w->dec_packed || w->dec_packed_floats != DEC_FLOATS || !w->dec_bwd_packed || w->dec_bwd_packed_floats != DECB_FLOATS) return DIF_EINVAL;
+    if (!has_dec(w) || !has_dec_bwd(w)) return DIF_EINVAL;
     if (N == 0 || n_iters == 0) return DIF_OK;
     if (!xyz || !normal || !unq_mask || !noise || !wsp || 8 * N + 64 >= (int64_t)1 << 31) return DIF_EINVAL;
     hipStream_t s = (hipStream_t)stream_;
@@ -693,8 +706,7 @@ int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const flo
     hipLaunchKernelGGL(k_optim_init, dim3(small), dim3(DIF_BLOCK), 0, s, (const int*)ws.uniq_slot, (const float*)map->latent_vecs, ws.z, ws.m, ws.v, ws.grad, (const int*)C);
     DIF_CHECK_LAUNCH();
     // the MLP tiles on the bf16 matrix pipe when the sliced blobs are there (as every other decoder launch), else on the f32-input MFMA
-    const bool x6 = w->dec_x6_packed && w->dec_x6_packed_bytes == X6_BYTES && w->dec_x6u_packed && w->dec_x6u_packed_bytes == X6U_BYTES &&
-                    w->dec_x6b_packed && w->dec_x6b_packed_bytes == X6B_BYTES;
+    const bool x6 = has_dec_x6(w) && has_dec_x6u(w) && has_dec_x6b(w);
     const size_t lds_bytes = x6 ? (size_t)X6_LDS_BYTES : (size_t)DEC_LDS_FLOATS * 4;
     static bool attr_set[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
@@ -725,10 +737,10 @@ int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const flo
 
 // ---- decoder launches ------------------------------------------------------------------------------------------
 static int launch_decode(const DecodeArgs& A, const dif_weights_t* w, int64_t tiles_upper, hipStream_t s) {
-    if (!w || !w->dec_packed || w->dec_packed_floats != DEC_FLOATS) return DIF_EINVAL;
+    if (!w || !has_dec(w)) return DIF_EINVAL;
     const bool grad = A.out_grad != nullptr;
     const bool dense = A.mode == 4;          // (the dense query of dif_sdf_hg: instantiations of their own, kernels_extract.hip.h)
-    if (grad && (!w->dec_bwd_packed || w->dec_bwd_packed_floats != DECB_FLOATS)) return DIF_EINVAL;
+    if (grad && !has_dec_bwd(w)) return DIF_EINVAL;
     const size_t lds_bytes = (size_t)DEC_LDS_FLOATS * 4;
     static bool attr_set[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
@@ -739,36 +751,31 @@ static int launch_decode(const DecodeArgs& A, const dif_weights_t* w, int64_t ti
         if (hipFuncSetAttribute((const void*)k_decode<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return DIF_ELAUNCH;
         attr_set[dev] = true;
     }
-    int64_t blocks = (tiles_upper + 7) / 8;
-    if (blocks < 1) blocks = 1;
-    if (blocks > num_cus()) blocks = num_cus();
+    int blocks = cu_blocks(tiles_upper, 8);
     ProfScope prof(A.mode == 0 ? DIF_PROF_DECODE_LATTICE : DIF_PROF_DECODE_POINTS, s);
-    if (!grad && A.mode != 1 && w->dec_x6_packed && w->dec_x6_packed_bytes == X6_BYTES && w->dec_x6u_packed && w->dec_x6u_packed_bytes == X6U_BYTES) {
+    if (!grad && A.mode != 1 && has_dec_x6(w) && has_dec_x6u(w)) {
         static bool attr_set6[64] = {};                      // forward-only rows on the bf16 matrix pipe
         if (dev < 64 && !attr_set6[dev]) {
             if (hipFuncSetAttribute((const void*)k_decode_x6<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
             if (hipFuncSetAttribute((const void*)k_decode_x6<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
             attr_set6[dev] = true;
         }
-        if (dense) hipLaunchKernelGGL(k_decode_x6<true>, dim3((int)blocks), dim3(512), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed, (const float*)w->dec_x6u_packed);
-        else hipLaunchKernelGGL(k_decode_x6<false>, dim3((int)blocks), dim3(512), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed, (const float*)w->dec_x6u_packed);
+        if (dense) hipLaunchKernelGGL(k_decode_x6<true>, dim3(blocks), dim3(512), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed, (const float*)w->dec_x6u_packed);
+        else hipLaunchKernelGGL(k_decode_x6<false>, dim3(blocks), dim3(512), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed, (const float*)w->dec_x6u_packed);
         DIF_CHECK_LAUNCH();
         return DIF_OK;
     }
-    if (grad && A.mode >= 2 && w->dec_x6_packed && w->dec_x6_packed_bytes == X6_BYTES && w->dec_x6u_packed && w->dec_x6u_packed_bytes == X6U_BYTES &&
-        w->dec_x6b_packed && w->dec_x6b_packed_bytes == X6B_BYTES) {
+    if (grad && A.mode >= 2 && has_dec_x6(w) && has_dec_x6u(w) && has_dec_x6b(w)) {
         static bool attr_set7[64] = {};                      // values + input gradient on the bf16 matrix pipe
         if (dev < 64 && !attr_set7[dev]) {
             if (hipFuncSetAttribute((const void*)k_decode_grad_x6<GRAD_X6_PF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
             if (hipFuncSetAttribute((const void*)k_decode_grad_x6<GRAD_X6_PF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
             attr_set7[dev] = true;
         }
-        blocks = (tiles_upper + GRAD_X6_THREADS / 64 - 1) / (GRAD_X6_THREADS / 64);
-        if (blocks < 1) blocks = 1;
-        if (blocks > num_cus()) blocks = num_cus();
-        if (dense) hipLaunchKernelGGL((k_decode_grad_x6<GRAD_X6_PF, true>), dim3((int)blocks), dim3(GRAD_X6_THREADS), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed,
+        blocks = cu_blocks(tiles_upper, GRAD_X6_THREADS / 64);
+        if (dense) hipLaunchKernelGGL((k_decode_grad_x6<GRAD_X6_PF, true>), dim3(blocks), dim3(GRAD_X6_THREADS), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed,
                                       (const float*)w->dec_x6u_packed, (const float*)w->dec_x6b_packed);
-        else hipLaunchKernelGGL(k_decode_grad_x6<GRAD_X6_PF>, dim3((int)blocks), dim3(GRAD_X6_THREADS), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed,
+        else hipLaunchKernelGGL(k_decode_grad_x6<GRAD_X6_PF>, dim3(blocks), dim3(GRAD_X6_THREADS), (size_t)X6_LDS_BYTES, s, A, (const float*)w->dec_x6_packed,
                                 (const float*)w->dec_x6u_packed, (const float*)w->dec_x6b_packed);
         DIF_CHECK_LAUNCH();
         return DIF_OK;
@@ -776,15 +783,13 @@ static int launch_decode(const DecodeArgs& A, const dif_weights_t* w, int64_t ti
     if (grad) {
         DecodeArgs B = A;
         B.wbwd = w->dec_bwd_packed;
-        blocks = (tiles_upper + 3) / 4;
-        if (blocks < 1) blocks = 1;
-        if (blocks > num_cus()) blocks = num_cus();
-        if (dense) hipLaunchKernelGGL((k_decode<true, true>), dim3((int)blocks), dim3(256), lds_bytes, s, B, w->dec_packed);
-        else hipLaunchKernelGGL(k_decode<true>, dim3((int)blocks), dim3(256), lds_bytes, s, B, w->dec_packed);
+        blocks = cu_blocks(tiles_upper, 4);
+        if (dense) hipLaunchKernelGGL((k_decode<true, true>), dim3(blocks), dim3(256), lds_bytes, s, B, w->dec_packed);
+        else hipLaunchKernelGGL(k_decode<true>, dim3(blocks), dim3(256), lds_bytes, s, B, w->dec_packed);
     } else if (dense) {
-        hipLaunchKernelGGL((k_decode<false, true>), dim3((int)blocks), dim3(512), lds_bytes, s, A, w->dec_packed);
+        hipLaunchKernelGGL((k_decode<false, true>), dim3(blocks), dim3(512), lds_bytes, s, A, w->dec_packed);
     } else {
-        hipLaunchKernelGGL(k_decode<false>, dim3((int)blocks), dim3(512), lds_bytes, s, A, w->dec_packed);
+        hipLaunchKernelGGL(k_decode<false>, dim3(blocks), dim3(512), lds_bytes, s, A, w->dec_packed);
     }
     DIF_CHECK_LAUNCH();
     return DIF_OK;
@@ -799,9 +804,9 @@ int dif_decode_rows(const dif_weights_t* w, const float* rows, int64_t n, float*
 }
 
 int dif_encode_rows(const dif_weights_t* w, const float* rows, int64_t n, float* out, void* stream) {
-    if (!w || !w->enc_packed || w->enc_packed_floats != ENC_FLOATS || n < 0 || (n > 0 && (!rows || !out))) return DIF_EINVAL;
+    if (!w || !has_enc(w) || n < 0 || (n > 0 && (!rows || !out))) return DIF_EINVAL;
     if (n == 0) return DIF_OK;
-    const bool x6 = w->enc_x6_packed && w->enc_x6_packed_bytes == E6_BYTES;
+    const bool x6 = has_enc_x6(w);
     const size_t lds_bytes = x6 ? (size_t)E6_BYTES : (size_t)ENC_FLOATS * 4;
     static bool attr_set[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
@@ -810,10 +815,9 @@ int dif_encode_rows(const dif_weights_t* w, const float* rows, int64_t n, float*
         if (hipFuncSetAttribute((const void*)k_encode_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)E6_BYTES) != hipSuccess) return DIF_ELAUNCH;
         attr_set[dev] = true;
     }
-    int64_t blocks = ((n + 31) / 32 + 7) / 8;
-    if (blocks > num_cus()) blocks = num_cus();
-    if (x6) hipLaunchKernelGGL(k_encode_rows<true>, dim3((int)blocks), dim3(512), lds_bytes, (hipStream_t)stream, (const float*)w->enc_x6_packed, rows, n, out);
-    else hipLaunchKernelGGL(k_encode_rows<false>, dim3((int)blocks), dim3(512), lds_bytes, (hipStream_t)stream, w->enc_packed, rows, n, out);
+    const int blocks = cu_blocks((n + 31) / 32, 8);
+    if (x6) hipLaunchKernelGGL(k_encode_rows<true>, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream, (const float*)w->enc_x6_packed, rows, n, out);
+    else hipLaunchKernelGGL(k_encode_rows<false>, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream, w->enc_packed, rows, n, out);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
@@ -970,16 +974,16 @@ static FinishArgs finish_args_of(const dif_map_t* map, const dif_extract_buffers
                       ov ? map->frame_counters : nullptr};
 }
 
+// LDS of the lattice kernel: the weights of its pipe + four pairs of waves
+constexpr size_t VD_LDS_F32 = ((size_t)((DEC_LDS_FLOATS + 3) & ~3) + 4 * VD_WAVE_LDS_FLOATS) * 4, VD_LDS_X6 = (size_t)X6_LDS_BYTES + 4 * VD_WAVE_LDS_FLOATS * 4;
 static int voxel_decode_attributes() {
     static bool attr_set[64] = {};
     int dev = 0; (void)hipGetDevice(&dev);
     if (dev < 64 && !attr_set[dev]) {
-        const int fp32_bytes = (int)(((size_t)((DEC_LDS_FLOATS + 3) & ~3) + 4 * VD_WAVE_LDS_FLOATS) * 4);
-        const int x6_bytes = (int)((size_t)X6_LDS_BYTES + 4 * VD_WAVE_LDS_FLOATS * 4);
-        if (hipFuncSetAttribute((const void*)k_decode_voxels<false>, hipFuncAttributeMaxDynamicSharedMemorySize, fp32_bytes) != hipSuccess) return DIF_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)k_decode_voxels<true>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_bytes) != hipSuccess) return DIF_ELAUNCH;
+        if (hipFuncSetAttribute((const void*)k_decode_voxels<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VD_LDS_F32) != hipSuccess) return DIF_ELAUNCH;
+        if (hipFuncSetAttribute((const void*)k_decode_voxels<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VD_LDS_X6) != hipSuccess) return DIF_ELAUNCH;
         if (hipFuncSetAttribute((const void*)k_decode_refine_x6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)k_decode_voxels_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_bytes) != hipSuccess) return DIF_ELAUNCH;
+        if (hipFuncSetAttribute((const void*)k_decode_voxels_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VD_LDS_X6) != hipSuccess) return DIF_ELAUNCH;
         if (hipFuncSetAttribute((const void*)k_decode_refine_x6_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_BYTES) != hipSuccess) return DIF_ELAUNCH;
         attr_set[dev] = true;
     }
@@ -1016,244 +1020,243 @@ static int mc_onepass_setup(const McArgs& a, size_t& lds_bytes, int& grid1, int6
     return DIF_OK;
 }
 
-static int extract_mesh_part(const dif_map_t* map, const dif_extract_buffers_t* buf, const ExtractGeo& e, float max_std, int32_t no_cache,
-                             int32_t scale_vertices, hipStream_t s);
+// the whole low lattice of the two-level chain (map.py:644-653) and the whole lattice of the exact chain (map.py:683-685; stored negated, map.py:687)
+static DecodeArgs low_lattice_args_of(const dif_map_t* map, const dif_extract_buffers_t* buf, const ExtractGeo& e) {
+    DecodeArgs A = {};
+    A.mode = 0; A.n_ptr = map->counters + DIF_C_B; A.occ_slot = buf->occ_slot; A.latent = map->latent_vecs;
+    A.lat.res = e.l; A.lat.a = (float)e.sample_a; A.lat.vsize = (e.l > 1) ? (float)((e.sample_b - e.sample_a) / (e.l - 1)) : 0.0f;
+    A.out_sdf = buf->low_sdf; A.out_std = buf->low_std; A.sign = 1.0f;
+    return A;
+}
+static DecodeArgs exact_lattice_args_of(const dif_map_t* map, const dif_extract_buffers_t* buf, const ExtractGeo& e) {
+    DecodeArgs A = {};
+    A.mode = 0; A.n_ptr = map->counters + DIF_C_B; A.occ_slot = buf->occ_slot; A.latent = map->latent_vecs;
+    A.lat.res = e.R; A.lat.a = (float)e.sample_a; A.lat.vsize = (float)((e.sample_b - e.sample_a) / (e.R - 1));
+    A.out_sdf = buf->cube_sdf; A.out_std = buf->cube_std; A.sign = -1.0f;
+    return A;
+}
 
-static int extract_impl(const dif_map_t* map, const dif_weights_t* w, const dif_extract_buffers_t* buf, int32_t resolution, int32_t fast,
-                        float max_std, int32_t no_cache, int32_t scale_vertices, void* stream_) {
+// Which chain of launches an extract runs: extract_plan decides, dif_extract launches any, dif_extract_streams one combination.
+// Dirty slots -> valid_blocks.  BlockTotals: k_dirty_scan — every writer of the flags kept the per-block totals (k_fuse; the host recomputes them
+// after anything else) and the map is whole 256-slot blocks: no counting pass.  BoundedTotals: launch_counted_scan_bounded — the totals are kept,
+// the capacity is small or ragged.  Generic: launch_scan with a counting pass — no totals, every slot dirty (no_cache), or a tiled map.
+enum class DirtyScan { BlockTotals, BoundedTotals, Generic };
+// FusedX6: per-voxel low lattice + upsample + threshold, then the balanced exact re-decode (map.py:644-679), both on the bf16 matrix pipe.
+// FusedF32: the same lattice kernel on the f32-input MFMA; launch_decode picks the kernel of the refine rows.  TwoLevel: a lattice too large
+// for the fused kernel — low lattice, k_upsample_mark, refine.  Exact (not fast): every lattice sample decoded exactly.
+enum class DecodeChain { FusedX6, FusedF32, TwoLevel, Exact };
+// OnePass: count, look-back and emit in one launch (mc_status, resolution <= 4).  CountEmit: count pass + emit pass, offsets through chunk_sum
+// (three levels of 256: max_voxels <= 2^24, beyond that the scan kernel).  CountScanEmit: count pass, scan kernel, emit pass.
+enum class McChain { OnePass, CountEmit, CountScanEmit };
+
+// Everything the launches of an extract need for ONE map, derived once from the C arguments (the counterpart of IntegratePlan): dif_extract passes
+// the pieces to the kernels by value, dif_extract_streams collects the pieces of S maps into the kernels' argument arrays.
+struct ExtractPlan {
+    ExtractGeo e;
+    DirtyScan scan; DecodeChain decode; McChain mc;
+    DirtySet dirty; const int* n_slots;       // dirty.tiled: k_mark_halo_dirty first
+    uint32_t* fused_word;                     // two queues: the word k_dirty_scan publishes for the front-end stream, else NULL
+    OccFunctor occ; int64_t grid;
+    VoxelDecodeArgs vd; size_t vd_lds; int vd_blocks;       // Fused*
+    DecodeArgs lattice; int64_t lattice_tiles;              // TwoLevel: the low lattice; Exact: the lattice
+    DecodeArgs refine; int64_t refine_tiles; int refine_blocks;      // all but Exact (refine_blocks: FusedX6, which launches k_decode_refine_x6 itself)
+    McArgs mc_args; size_t mc_lds; int mc_grid;             // (CountScanEmit: mc_count_and_scan / mc_emit complete and shape their own)
+    FinishArgs finish; int finish_grid;       // (finish.mc_status / finish.mc_ticket: the one-pass kernel's look-back words)
+};
+
+static int extract_plan(const dif_map_t* map, const dif_weights_t* w, const dif_extract_buffers_t* buf, int resolution, int fast, float max_std,
+                        int no_cache, int scale_vertices, hipStream_t s, ExtractPlan& P) {
     if (!map || !w || !buf || resolution < 1 || resolution > 8 || buf->max_voxels <= 0) return DIF_EINVAL;
-    const int* n_slots = map->counters + DIF_C_N_OCCUPIED;
     if (!map->grid_tot) return DIF_EINVAL;
-    const GridMarks bits = grid_marks_of(map);
     if (buf->cache_capacity <= 0 || buf->cache_capacity >= ((int64_t)1 << 31) || !buf->cache_tri || !buf->cache_id || !buf->cache_std || !buf->cache_alive)
         return DIF_EINVAL;
     if (!map->tri_start || !map->tri_n) return DIF_EINVAL;
-    hipStream_t s = (hipStream_t)stream_;
-    const int64_t grid = (int64_t)map->nx * map->ny * map->nz;
-    Geo g = geo_of(map);
-    int* C = map->counters;
     // two queues: this extract follows the frame's fusion kernel on ITS stream (dif_map_t.fuse_stream); its first kernel tells the front-end
     // stream that the fusion is done
     const bool ov = overlapped(map);
-    if (ov && (!overlap_ok(map) || no_cache || defer_export_of(map, buf) || s != (hipStream_t)map->fuse_stream)) return DIF_EINVAL;
-    const ExtractGeo e = extract_geo(resolution);
-    const int r = e.r, R = e.R, l = e.l, R3 = e.R3;
-    if (buf->max_voxels * (int64_t)R3 >= ((int64_t)1 << 31)) return DIF_EINVAL;
-    const double sample_a = e.sample_a, sample_b = e.sample_b;
+    const bool defer = defer_export_of(map, buf);
+    if (ov && (!overlap_ok(map) || no_cache || defer || s != (hipStream_t)map->fuse_stream)) return DIF_EINVAL;
+    const ExtractGeo e = P.e = extract_geo(resolution);
+    const int64_t max_voxels = buf->max_voxels;
+    if (max_voxels * (int64_t)e.R3 >= ((int64_t)1 << 31)) return DIF_EINVAL;
 
-    {   // dirty slots -> valid_blocks
-        const DirtySet ds = dirty_set_of(map, buf, no_cache);
-        const bool tiled = ds.tiled;
-        if (tiled) {
-            hipLaunchKernelGGL(k_mark_halo_dirty, dim3(grid_for(map->capacity, DIF_BLOCK, 256)), dim3(DIF_BLOCK), 0, s, g, map->ignore_count_th, map->dirty,
-                               (const int64_t*)map->latent_vecs_pos, (const int64_t*)map->indexer, (const float*)map->voxel_obs_count, bits,
-                               n_slots, ds.own_lin_lo, ds.own_lin_hi);
-            DIF_CHECK_LAUNCH();
-        }
-        {
-            DirtyFunctor f{ds};
-            // every writer of the flags kept the per-block totals (k_fuse; the host recomputes them after anything else): no counting pass
-            if (map->dirty_tot && !no_cache && !tiled && map->capacity > 4096 && map->capacity % DIF_BLOCK == 0) {
-                hipLaunchKernelGGL(k_dirty_scan, dim3((int)(map->capacity / DIF_BLOCK)), dim3(DIF_BLOCK), 0, s, ds, n_slots, (const int*)map->dirty_tot,
-                                   ov ? map->sync_words + DIF_SYNC_FUSED : nullptr, (int)map->frame_seq);
-                DIF_CHECK_LAUNCH();
-            } else if (ov) {
-                return DIF_EINVAL;          // (overlap_ok() admits only maps that take the launch above: it publishes DIF_SYNC_FUSED)
-            } else if (map->dirty_tot && !no_cache && !tiled) {
-                if (launch_counted_scan_bounded(f, n_slots, map->capacity, map->dirty_tot, s) != DIF_OK) return DIF_ELAUNCH;
-            } else if (launch_scan(f, n_slots, 0, map->capacity, buf->block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
-        }
-    }
-    {
-        OccFunctor f{map->grid_bits, map->indexer, buf->occ_slot, map->vbm, C, buf->max_voxels};
-        if (launch_counted_scan(f, (int)((grid + 31) / 32), map->grid_tot, s) != DIF_OK) return DIF_ELAUNCH;      // the markers kept the block totals
-    }
-    int rc;
-    if (fast && l * l * l <= VD_MAX_L3 && R * R <= VD_MAX_R2) {
-        // fused per-voxel low lattice + upsample + threshold, then the balanced exact re-decode (map.py:644-679)
-        if (!w->dec_packed || w->dec_packed_floats != DEC_FLOATS) return DIF_EINVAL;
-        const bool fold = w->dec_fold_packed && w->dec_fold_packed_floats == DECF_FLOATS && buf->fold_table;
-        const VoxelDecodeArgs V = voxel_decode_args_of(map, w, buf, e, fold);
-        const bool x6 = fold && w->dec_x6_packed && w->dec_x6_packed_bytes == X6_BYTES;       // tiles on the bf16 matrix pipe (mlp.hip.h)
-        const size_t lds_bytes = x6 ? (size_t)X6_LDS_BYTES + 4 * VD_WAVE_LDS_FLOATS * 4
-                                    : ((size_t)((DEC_LDS_FLOATS + 3) & ~3) + 4 * VD_WAVE_LDS_FLOATS) * 4;       // four pairs of waves
-        if (voxel_decode_attributes() != DIF_OK) return DIF_ELAUNCH;
-        int64_t blocks = (buf->max_voxels + 3) / 4;
-        if (blocks > num_cus()) blocks = num_cus();
-        {
-            ProfScope prof(DIF_PROF_DECODE_LATTICE, s);
-            if (x6) hipLaunchKernelGGL(k_decode_voxels<true>, dim3((int)blocks), dim3(512), lds_bytes, s, V, (const float*)w->dec_x6_packed);
-            else hipLaunchKernelGGL(k_decode_voxels<false>, dim3((int)blocks), dim3(512), lds_bytes, s, V, w->dec_packed);
-        }
-        DIF_CHECK_LAUNCH();
-        const DecodeArgs Rf = refine_args_of(map, buf, e, fold);
-        if (x6) {
-            int64_t rblocks = (buf->max_voxels * (int64_t)(R3 / 32) + 7) / 8;
-            if (rblocks < 1) rblocks = 1;
-            if (rblocks > num_cus()) rblocks = num_cus();
-            ProfScope prof(DIF_PROF_DECODE_POINTS, s);
-            hipLaunchKernelGGL(k_decode_refine_x6, dim3((int)rblocks), dim3(512), (size_t)X6_LDS_BYTES, s, Rf, (const float*)w->dec_x6_packed);
-            DIF_CHECK_LAUNCH();
-            rc = DIF_OK;
-        } else {
-            rc = launch_decode(Rf, w, buf->max_voxels * (int64_t)(R3 / 32), s);
-        }
-        if (rc != DIF_OK) return rc;
-    } else if (fast) {
-        // low lattice decode (map.py:644-653)
-        DecodeArgs A = {};
-        A.mode = 0; A.n_ptr = C + DIF_C_B; A.occ_slot = buf->occ_slot; A.latent = map->latent_vecs;
-        A.lat.res = l; A.lat.a = (float)sample_a;
-        A.lat.vsize = (l > 1) ? (float)((sample_b - sample_a) / (l - 1)) : 0.0f;
-        A.out_sdf = buf->low_sdf; A.out_std = buf->low_std; A.sign = 1.0f;
-        rc = launch_decode(A, w, buf->max_voxels * ((l * l * l + 31) / 32), s);
-        if (rc != DIF_OK) return rc;
-        // upsample + threshold (map.py:655-667)
-        hipLaunchKernelGGL(k_upsample_mark, dim3(grid_for(buf->max_voxels * (int64_t)(R * R), DIF_BLOCK, 4096)), dim3(DIF_BLOCK), 0, s,
-                           (const float*)buf->low_sdf, (const float*)buf->low_std, l, R, buf->cube_sdf, buf->cube_std, buf->refine_list, C);
-        DIF_CHECK_LAUNCH();
-        // exact re-decode of the near-surface samples (map.py:668-679)
-        const DecodeArgs Rf = refine_args_of(map, buf, e, false);
-        rc = launch_decode(Rf, w, buf->max_voxels * (int64_t)(R3 / 32), s);
-        if (rc != DIF_OK) return rc;
+    P.dirty = dirty_set_of(map, buf, no_cache);
+    P.n_slots = map->counters + DIF_C_N_OCCUPIED;
+    const bool totals = map->dirty_tot && !no_cache && !P.dirty.tiled;
+    P.scan = !totals ? DirtyScan::Generic : (map->capacity > 4096 && map->capacity % DIF_BLOCK == 0) ? DirtyScan::BlockTotals : DirtyScan::BoundedTotals;
+    if (ov && P.scan != DirtyScan::BlockTotals) return DIF_EINVAL;      // (overlap_ok() admits only such maps: k_dirty_scan publishes DIF_SYNC_FUSED)
+    P.fused_word = ov ? map->sync_words + DIF_SYNC_FUSED : nullptr;
+    P.grid = (int64_t)map->nx * map->ny * map->nz;
+    P.occ = OccFunctor{map->grid_bits, map->indexer, buf->occ_slot, map->vbm, map->counters, max_voxels};
+
+    if (!has_dec(w)) return DIF_EINVAL;
+    const bool fused = fast && e.l * e.l * e.l <= VD_MAX_L3 && e.R * e.R <= VD_MAX_R2;
+    const bool fold = fused && has_dec_fold(w) && buf->fold_table;
+    P.decode = !fast ? DecodeChain::Exact : !fused ? DecodeChain::TwoLevel : (fold && has_dec_x6(w)) ? DecodeChain::FusedX6 : DecodeChain::FusedF32;
+    P.refine_tiles = max_voxels * (int64_t)(e.R3 / 32);
+    if (P.decode == DecodeChain::Exact) {
+        P.lattice = exact_lattice_args_of(map, buf, e);
+        P.lattice_tiles = max_voxels * (int64_t)((e.R3 + 31) / 32);
+    } else if (P.decode == DecodeChain::TwoLevel) {
+        P.lattice = low_lattice_args_of(map, buf, e);
+        P.lattice_tiles = max_voxels * ((e.l * e.l * e.l + 31) / 32);
+        P.refine = refine_args_of(map, buf, e, false);
     } else {
-        // every lattice sample decoded exactly (map.py:683-685), stored negated (map.py:687)
-        DecodeArgs A = {};
-        A.mode = 0; A.n_ptr = C + DIF_C_B; A.occ_slot = buf->occ_slot; A.latent = map->latent_vecs;
-        A.lat.res = R; A.lat.a = (float)sample_a; A.lat.vsize = (float)((sample_b - sample_a) / (R - 1));
-        A.out_sdf = buf->cube_sdf; A.out_std = buf->cube_std; A.sign = -1.0f;
-        rc = launch_decode(A, w, buf->max_voxels * (int64_t)((R3 + 31) / 32), s);
-        if (rc != DIF_OK) return rc;
+        P.vd = voxel_decode_args_of(map, w, buf, e, fold);
+        if (voxel_decode_attributes() != DIF_OK) return DIF_ELAUNCH;
+        P.vd_lds = P.decode == DecodeChain::FusedX6 ? VD_LDS_X6 : VD_LDS_F32;
+        P.vd_blocks = cu_blocks(max_voxels, 4);
+        P.refine = refine_args_of(map, buf, e, fold);
+        P.refine_blocks = cu_blocks(P.refine_tiles, 8);
     }
-    return extract_mesh_part(map, buf, e, max_std, no_cache, scale_vertices, s);
+
+    // marching cubes (map.py:689-691), mesh-cache bookkeeping, counter snapshot
+    P.mc_args = mc_args_of(map, buf, e, max_std, scale_vertices);
+    const bool chunked = buf->chunk_sum && max_voxels <= ((int64_t)1 << 24);      // the triangle offsets go through chunk_sum
+    P.mc = !chunked ? McChain::CountScanEmit : (buf->mc_status && e.r * e.r * e.r <= 64) ? McChain::OnePass : McChain::CountEmit;
+    int rc = DIF_OK;
+    if (P.mc == McChain::OnePass) {
+        mc_onepass_args(P.mc_args, map, buf, defer);
+        rc = mc_onepass_setup(P.mc_args, P.mc_lds, P.mc_grid, max_voxels);
+    } else if (P.mc == McChain::CountEmit) {
+        McArgs& a = P.mc_args;
+        a.chunk_sum = buf->chunk_sum; a.super_sum = buf->chunk_sum + (max_voxels + 255) / 256; a.tri_start = map->tri_start; a.tri_n = map->tri_n;
+        a.tri_count = buf->tri_count; a.tri_offset = nullptr;
+        rc = mc_setup(a, P.mc_lds, P.mc_grid, max_voxels);
+    }
+    if (rc != DIF_OK) return rc;
+    // (out_tri: set by mc_onepass_args alone — only the one-pass kernel writes the caller's copy)
+    P.finish = finish_args_of(map, buf, chunked, P.mc == McChain::OnePass, P.mc_args.out_tri != nullptr, defer);
+    P.finish_grid = grid_for(max_voxels, DIF_BLOCK, 256);
+    return DIF_OK;
 }
 
-// marching cubes (map.py:689-691), mesh-cache bookkeeping, counter snapshot: the second half of an extract
-static int extract_mesh_part(const dif_map_t* map, const dif_extract_buffers_t* buf, const ExtractGeo& e, float max_std, int32_t no_cache,
-                             int32_t scale_vertices, hipStream_t s) {
+int dif_extract(const dif_map_t* map, const dif_weights_t* w, const dif_extract_buffers_t* buf, int32_t resolution, int32_t fast,
+                float max_std, int32_t no_cache, int32_t scale_vertices, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    ExtractPlan P;
+    int rc = extract_plan(map, w, buf, resolution, fast, max_std, no_cache, scale_vertices, s, P);
+    if (rc != DIF_OK) return rc;
     int* C = map->counters;
-    const int r = e.r;
-    int rc;
-    McArgs a = mc_args_of(map, buf, e, max_std, scale_vertices);
+    const ExtractGeo& e = P.e;
+    if (P.dirty.tiled) {
+        hipLaunchKernelGGL(k_mark_halo_dirty, dim3(grid_for(map->capacity, DIF_BLOCK, 256)), dim3(DIF_BLOCK), 0, s, geo_of(map), map->ignore_count_th, map->dirty,
+                           (const int64_t*)map->latent_vecs_pos, (const int64_t*)map->indexer, (const float*)map->voxel_obs_count, grid_marks_of(map),
+                           P.n_slots, P.dirty.own_lin_lo, P.dirty.own_lin_hi);
+        DIF_CHECK_LAUNCH();
+    }
+    if (P.scan == DirtyScan::BlockTotals) {
+        hipLaunchKernelGGL(k_dirty_scan, dim3((int)(map->capacity / DIF_BLOCK)), dim3(DIF_BLOCK), 0, s, P.dirty, P.n_slots, (const int*)map->dirty_tot,
+                           P.fused_word, (int)map->frame_seq);
+        DIF_CHECK_LAUNCH();
+    } else if (P.scan == DirtyScan::BoundedTotals) {
+        if (launch_counted_scan_bounded(DirtyFunctor{P.dirty}, P.n_slots, map->capacity, map->dirty_tot, s) != DIF_OK) return DIF_ELAUNCH;
+    } else if (launch_scan(DirtyFunctor{P.dirty}, P.n_slots, 0, map->capacity, buf->block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+    if (launch_counted_scan(P.occ, (int)((P.grid + 31) / 32), map->grid_tot, s) != DIF_OK) return DIF_ELAUNCH;      // the markers kept the block totals
+
+    if (P.decode == DecodeChain::FusedX6 || P.decode == DecodeChain::FusedF32) {
+        const bool x6 = P.decode == DecodeChain::FusedX6;
+        {
+            ProfScope prof(DIF_PROF_DECODE_LATTICE, s);
+            if (x6) hipLaunchKernelGGL(k_decode_voxels<true>, dim3(P.vd_blocks), dim3(512), P.vd_lds, s, P.vd, (const float*)w->dec_x6_packed);
+            else hipLaunchKernelGGL(k_decode_voxels<false>, dim3(P.vd_blocks), dim3(512), P.vd_lds, s, P.vd, w->dec_packed);
+        }
+        DIF_CHECK_LAUNCH();
+        if (x6) {
+            ProfScope prof(DIF_PROF_DECODE_POINTS, s);
+            hipLaunchKernelGGL(k_decode_refine_x6, dim3(P.refine_blocks), dim3(512), (size_t)X6_LDS_BYTES, s, P.refine, (const float*)w->dec_x6_packed);
+            DIF_CHECK_LAUNCH();
+        } else if ((rc = launch_decode(P.refine, w, P.refine_tiles, s)) != DIF_OK) return rc;
+    } else {
+        if ((rc = launch_decode(P.lattice, w, P.lattice_tiles, s)) != DIF_OK) return rc;
+        if (P.decode == DecodeChain::TwoLevel) {
+            // upsample + threshold (map.py:655-667), then the exact re-decode of the near-surface samples (map.py:668-679)
+            hipLaunchKernelGGL(k_upsample_mark, dim3(grid_for(buf->max_voxels * (int64_t)(e.R * e.R), DIF_BLOCK, 4096)), dim3(DIF_BLOCK), 0, s,
+                               (const float*)buf->low_sdf, (const float*)buf->low_std, e.l, e.R, buf->cube_sdf, buf->cube_std, buf->refine_list, C);
+            DIF_CHECK_LAUNCH();
+            if ((rc = launch_decode(P.refine, w, P.refine_tiles, s)) != DIF_OK) return rc;
+        }
+    }
+
     if (no_cache) {                                                                                               // map.py:614-616
         if (hipMemsetAsync(C + DIF_C_CACHE_T, 0, sizeof(int), s) != hipSuccess) return DIF_ELAUNCH;
         if (hipMemsetAsync(C + DIF_C_CACHE_DEAD, 0, sizeof(int), s) != hipSuccess) return DIF_ELAUNCH;
         if (hipMemsetAsync(map->tri_n, 0, sizeof(int32_t) * (size_t)map->capacity, s) != hipSuccess) return DIF_ELAUNCH;
     }
-    const bool defer = defer_export_of(map, buf);
-    const bool fused_scan = buf->chunk_sum && buf->max_voxels <= ((int64_t)1 << 24);      // three levels of 256: beyond that the scan kernel
-    int32_t* const super_sum = buf->chunk_sum ? buf->chunk_sum + (buf->max_voxels + 255) / 256 : nullptr;
-    const bool onepass = fused_scan && buf->mc_status && r * r * r <= 64;                // count, look-back and emit in one launch
-    if (onepass) {
-        mc_onepass_args(a, map, buf, defer);
-        size_t lds_bytes; int grid1;
-        rc = mc_onepass_setup(a, lds_bytes, grid1, buf->max_voxels);
-        if (rc != DIF_OK) return rc;
+    if (P.mc == McChain::OnePass) {
         {
             ProfScope prof(DIF_PROF_MC_COUNT, s);
             // (resolution 4 — main.py:93's — with the resolution as a compile-time constant)
-            if (r == 4) hipLaunchKernelGGL(k_marching_cubes_onepass<4>, dim3(grid1), dim3(DIF_BLOCK), lds_bytes, s, a, buf->mc_status, buf->mc_status + (buf->max_voxels + 3) / 4);
-            else hipLaunchKernelGGL(k_marching_cubes_onepass<0>, dim3(grid1), dim3(DIF_BLOCK), lds_bytes, s, a, buf->mc_status, buf->mc_status + (buf->max_voxels + 3) / 4);
+            if (e.r == 4) hipLaunchKernelGGL(k_marching_cubes_onepass<4>, dim3(P.mc_grid), dim3(DIF_BLOCK), P.mc_lds, s, P.mc_args, P.finish.mc_status, P.finish.mc_ticket);
+            else hipLaunchKernelGGL(k_marching_cubes_onepass<0>, dim3(P.mc_grid), dim3(DIF_BLOCK), P.mc_lds, s, P.mc_args, P.finish.mc_status, P.finish.mc_ticket);
         }
         DIF_CHECK_LAUNCH();
-    } else if (fused_scan) {
-        a.chunk_sum = buf->chunk_sum; a.super_sum = super_sum; a.tri_start = map->tri_start; a.tri_n = map->tri_n;
-        a.tri_count = buf->tri_count; a.tri_offset = nullptr;
-        size_t lds_bytes; int blocks;
-        rc = mc_setup(a, lds_bytes, blocks, buf->max_voxels);
-        if (rc != DIF_OK) return rc;
+    } else if (P.mc == McChain::CountEmit) {
         {
             ProfScope prof(DIF_PROF_MC_COUNT, s);
-            hipLaunchKernelGGL(k_marching_cubes<false>, dim3(blocks), dim3(DIF_BLOCK), lds_bytes, s, a);
+            hipLaunchKernelGGL(k_marching_cubes<false>, dim3(P.mc_grid), dim3(DIF_BLOCK), P.mc_lds, s, P.mc_args);
         }
         {
             ProfScope prof(DIF_PROF_MC_EMIT, s);
-            hipLaunchKernelGGL(k_marching_cubes<true>, dim3(blocks), dim3(DIF_BLOCK), lds_bytes, s, a);
+            hipLaunchKernelGGL(k_marching_cubes<true>, dim3(P.mc_grid), dim3(DIF_BLOCK), P.mc_lds, s, P.mc_args);
         }
         DIF_CHECK_LAUNCH();
     } else {
         TriScanFunctor ts{};
         ts.valid_blocks = buf->valid_blocks; ts.indexer = map->indexer; ts.tri_start = map->tri_start; ts.tri_n = map->tri_n; ts.alive = buf->cache_alive;
         ts.new_limit = buf->max_triangles; ts.capacity = buf->cache_capacity;
-        rc = mc_count_and_scan(a, buf->max_voxels, buf->tri_count, buf->tri_offset, buf->block_tmp, C, ts, s);
-        if (rc != DIF_OK) return rc;
-        rc = mc_emit(a, buf->max_voxels, buf->tri_count, buf->tri_offset, s);
-        if (rc != DIF_OK) return rc;
+        if ((rc = mc_count_and_scan(P.mc_args, buf->max_voxels, buf->tri_count, buf->tri_offset, buf->block_tmp, C, ts, s)) != DIF_OK) return rc;
+        if ((rc = mc_emit(P.mc_args, buf->max_voxels, buf->tri_count, buf->tri_offset, s)) != DIF_OK) return rc;
     }
-    hipLaunchKernelGGL(k_extract_finish, dim3(grid_for(buf->max_voxels, DIF_BLOCK, 256)), dim3(DIF_BLOCK), 0, s,
-                       finish_args_of(map, buf, fused_scan, onepass, onepass && a.out_tri, defer));
+    hipLaunchKernelGGL(k_extract_finish, dim3(P.finish_grid), dim3(DIF_BLOCK), 0, s, P.finish);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
 
 // S maps through the six launches of the stream's extract (dirty scan, batch scan, lattice decode, refine decode, one-pass marching cubes,
-// finish): only the configuration a streaming caller runs — see include/difusion.h
+// finish): only the configuration a streaming caller runs, which is the one extract_plan classifies as BlockTotals, not tiled, FusedX6 and
+// OnePass with fast = 1, no_cache = 0 — see include/difusion.h
 int dif_extract_streams(const dif_stream_frame_t* st, int32_t S, const dif_weights_t* w, int32_t resolution, float max_std, int32_t scale_vertices,
                         void* stream_) {
-    if (!batch_maps_ok(st, S) || !w || resolution < 1 || resolution > 4) return DIF_EINVAL;
-    const ExtractGeo e = extract_geo(resolution);
-    if (e.l * e.l * e.l > VD_MAX_L3 || e.R * e.R > VD_MAX_R2 || e.r * e.r * e.r > 64) return DIF_EINVAL;
-    if (!w->dec_packed || w->dec_packed_floats != DEC_FLOATS || !w->dec_fold_packed || w->dec_fold_packed_floats != DECF_FLOATS || !w->dec_x6_packed ||
-        w->dec_x6_packed_bytes != X6_BYTES)
-        return DIF_EINVAL;
-    const dif_map_t* m0 = st[0].map;
-    if (m0->capacity <= 4096 || m0->capacity % DIF_BLOCK != 0) return DIF_EINVAL;
-    const int64_t grid = (int64_t)m0->nx * m0->ny * m0->nz;
+    if (!batch_maps_ok(st, S)) return DIF_EINVAL;          // (no map of a batch is overlapped: every plan's fused_word is NULL)
+    hipStream_t s = (hipStream_t)stream_;
     static thread_local Batch<DirtyScanArgs> dirty; static thread_local ScanBatch<OccFunctor> occ; static thread_local Batch<VoxelDecodeArgs> vd;
     static thread_local Batch<DecodeArgs> rf; static thread_local Batch<McStream> mc; static thread_local Batch<FinishArgs> fin;
+    ExtractPlan P;          // (what is left in it after the loop — geometry and shapes — is the same for every map: one capacity, one grid, one max_voxels)
     for (int j = 0; j < S; ++j) {
-        const dif_map_t* map = st[j].map;
-        const dif_extract_buffers_t* buf = st[j].buf;
-        if (!buf || buf->max_voxels <= 0 || buf->max_voxels != st[0].buf->max_voxels || buf->max_voxels * (int64_t)e.R3 >= ((int64_t)1 << 31)) return DIF_EINVAL;
-        if (buf->cache_capacity <= 0 || buf->cache_capacity >= ((int64_t)1 << 31) || !buf->cache_tri || !buf->cache_id || !buf->cache_std || !buf->cache_alive)
-            return DIF_EINVAL;
-        if (!map->tri_start || !map->tri_n || !buf->fold_table || !buf->chunk_sum || !buf->mc_status || buf->max_voxels > ((int64_t)1 << 24)) return DIF_EINVAL;
-        dirty.s[j] = DirtyScanArgs{dirty_set_of(map, buf, 0), map->counters + DIF_C_N_OCCUPIED, map->dirty_tot};
-        occ.f[j] = OccFunctor{map->grid_bits, map->indexer, buf->occ_slot, map->vbm, map->counters, buf->max_voxels};
-        occ.tot[j] = map->grid_tot;
-        vd.s[j] = voxel_decode_args_of(map, w, buf, e, true);
-        rf.s[j] = refine_args_of(map, buf, e, true);
-        const bool defer = defer_export_of(map, buf);
-        McArgs a = mc_args_of(map, buf, e, max_std, scale_vertices);
-        mc_onepass_args(a, map, buf, defer);
-        mc.s[j] = McStream{a, buf->mc_status, buf->mc_status + (buf->max_voxels + 3) / 4};
-        fin.s[j] = finish_args_of(map, buf, true, true, a.out_tri != nullptr, defer);
+        const int rc = extract_plan(st[j].map, w, st[j].buf, resolution, 1, max_std, 0, scale_vertices, s, P);
+        if (rc != DIF_OK) return rc;
+        if (P.scan != DirtyScan::BlockTotals || P.dirty.tiled || P.decode != DecodeChain::FusedX6 || P.mc != McChain::OnePass) return DIF_EINVAL;
+        if (st[j].buf->max_voxels != st[0].buf->max_voxels) return DIF_EINVAL;
+        dirty.s[j] = DirtyScanArgs{P.dirty, P.n_slots, st[j].map->dirty_tot};
+        occ.f[j] = P.occ; occ.tot[j] = st[j].map->grid_tot;
+        vd.s[j] = P.vd; rf.s[j] = P.refine;
+        mc.s[j] = McStream{P.mc_args, P.finish.mc_status, P.finish.mc_ticket};
+        fin.s[j] = P.finish;
     }
     for (int j = S; j < DIF_MAX_STREAMS; ++j) {
         dirty.s[j] = dirty.s[0]; occ.f[j] = occ.f[0]; occ.tot[j] = occ.tot[0]; vd.s[j] = vd.s[0]; rf.s[j] = rf.s[0]; mc.s[j] = mc.s[0]; fin.s[j] = fin.s[0];
     }
-    hipStream_t s = (hipStream_t)stream_;
-    const int64_t max_voxels = st[0].buf->max_voxels;
-    hipLaunchKernelGGL(k_dirty_scan_batch, dim3((int)(m0->capacity / DIF_BLOCK), S), dim3(DIF_BLOCK), 0, s, dirty);
+    hipLaunchKernelGGL(k_dirty_scan_batch, dim3((int)(st[0].map->capacity / DIF_BLOCK), S), dim3(DIF_BLOCK), 0, s, dirty);
     DIF_CHECK_LAUNCH();
-    if (launch_counted_scan_batch(occ, S, (int)((grid + 31) / 32), s) != DIF_OK) return DIF_ELAUNCH;
-    if (voxel_decode_attributes() != DIF_OK) return DIF_ELAUNCH;
-    {
-        int64_t blocks = (max_voxels * S + 3) / 4;
-        if (blocks > num_cus()) blocks = num_cus();
+    if (launch_counted_scan_batch(occ, S, (int)((P.grid + 31) / 32), s) != DIF_OK) return DIF_ELAUNCH;
+    {   // the S maps' voxels and refine tiles are one range each to these two kernels: S times the plan's items over the CUs
         ProfScope prof(DIF_PROF_DECODE_LATTICE, s);
-        hipLaunchKernelGGL(k_decode_voxels_batch<true>, dim3((int)blocks), dim3(512), (size_t)X6_LDS_BYTES + 4 * VD_WAVE_LDS_FLOATS * 4, s, vd, (int)S,
-                           (const float*)w->dec_x6_packed);
+        hipLaunchKernelGGL(k_decode_voxels_batch<true>, dim3(cu_blocks(P.occ.max_voxels * S, 4)), dim3(512), P.vd_lds, s, vd, (int)S, (const float*)w->dec_x6_packed);
         DIF_CHECK_LAUNCH();
     }
     {
-        int64_t rblocks = (max_voxels * S * (int64_t)(e.R3 / 32) + 7) / 8;
-        if (rblocks < 1) rblocks = 1;
-        if (rblocks > num_cus()) rblocks = num_cus();
         ProfScope prof(DIF_PROF_DECODE_POINTS, s);
-        hipLaunchKernelGGL(k_decode_refine_x6_batch, dim3((int)rblocks), dim3(512), (size_t)X6_LDS_BYTES, s, rf, (int)S, (const float*)w->dec_x6_packed);
+        hipLaunchKernelGGL(k_decode_refine_x6_batch, dim3(cu_blocks(P.refine_tiles * S, 8)), dim3(512), (size_t)X6_LDS_BYTES, s, rf, (int)S, (const float*)w->dec_x6_packed);
         DIF_CHECK_LAUNCH();
     }
     {
-        size_t lds_bytes; int grid1;
-        const int rc = mc_onepass_setup(mc.s[0].a, lds_bytes, grid1, max_voxels);
-        if (rc != DIF_OK) return rc;
         ProfScope prof(DIF_PROF_MC_COUNT, s);
-        if (e.r == 4) hipLaunchKernelGGL(k_marching_cubes_onepass_batch<4>, dim3(grid1, S), dim3(DIF_BLOCK), lds_bytes, s, mc);
-        else hipLaunchKernelGGL(k_marching_cubes_onepass_batch<0>, dim3(grid1, S), dim3(DIF_BLOCK), lds_bytes, s, mc);
+        if (P.e.r == 4) hipLaunchKernelGGL(k_marching_cubes_onepass_batch<4>, dim3(P.mc_grid, S), dim3(DIF_BLOCK), P.mc_lds, s, mc);
+        else hipLaunchKernelGGL(k_marching_cubes_onepass_batch<0>, dim3(P.mc_grid, S), dim3(DIF_BLOCK), P.mc_lds, s, mc);
         DIF_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_extract_finish_batch, dim3(grid_for(max_voxels, DIF_BLOCK, 256), S), dim3(DIF_BLOCK), 0, s, fin);
+    hipLaunchKernelGGL(k_extract_finish_batch, dim3(P.finish_grid, S), dim3(DIF_BLOCK), 0, s, fin);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
@@ -1266,11 +1269,6 @@ int dif_trace_read_encode(unsigned long long* out, int64_t n) {      // host cop
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_en_trace), (size_t)n * 8) == hipSuccess ? DIF_OK : DIF_ELAUNCH;
 }
 #endif
-
-int dif_extract(const dif_map_t* map, const dif_weights_t* w, const dif_extract_buffers_t* buf, int32_t resolution, int32_t fast,
-                float max_std, int32_t no_cache, int32_t scale_vertices, void* stream_) {
-    return extract_impl(map, w, buf, resolution, fast, max_std, no_cache, scale_vertices, stream_);
-}
 
 int dif_export_pending(const dif_map_t* map, void* stream) {
     if (!map) return DIF_EINVAL;

@@ -366,7 +366,9 @@ int dif_export_pending(const dif_map_t* map, void* stream);
  * Every stream's results are bit-identical to dif_integrate_frame + dif_extract on that stream alone.
  * Requirements (else DIF_EINVAL): the maps have the same nx, ny, nz and capacity, are not spatially tiled, carry dirty_tot / grid_tot /
  * pending_export like a streaming map; the extract buffers have the same max_voxels, chunk_sum / mc_status / fold_table set; the weights
- * carry the bf16-sliced blobs (the default pipe); resolution <= 4, fast two-level decode. */
+ * carry the bf16-sliced blobs (the default pipe); resolution <= 4, fast two-level decode.  That list is not written out in the library: it
+ * is the configuration extract_plan (csrc/difusion.hip) classifies, with fast = 1 and no_cache = 0, as BlockTotals (dirty_tot kept, a
+ * capacity above 4,096 in whole 256-slot blocks), not tiled, FusedX6 and OnePass — the same classification dif_extract launches from. */
 typedef struct dif_stream_frame {
     const dif_map_t* map;                   /* [host] */
     const dif_frame_t* frame_dev;           /* as dif_integrate_frame */

@@ -851,8 +851,10 @@ def test_dirty_set_block_totals_match_the_counting_pass(gpu_model):
         assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), i
 
 
-def test_one_pass_marching_cubes_equals_count_and_emit_passes(gpu_model):
-    """The stream path's single-launch marching cubes (count, decoupled look-back, emit) against the count pass + emit pass it replaces:
+@pytest.mark.parametrize("withheld", [("mc_status",), ("chunk_sum", "mc_status")], ids=["count_emit", "count_scan_emit"])
+def test_one_pass_marching_cubes_equals_count_and_emit_passes(withheld, gpu_model):
+    """The stream path's single-launch marching cubes (count, decoupled look-back, emit) against the passes it replaces — without mc_status
+    the count pass + emit pass over chunk_sum, without chunk_sum as well the count pass, the scan kernel and the emit pass:
     12.8 k dirty voxels (3,200 look-back groups over 512 resident workgroups, i.e. several groups per workgroup), then a second frame
     that replaces batches in the log — the same log, bit for bit, and the same bookkeeping."""
     from di_fusion_amd.system.map import DenseIndexedMap
@@ -877,12 +879,13 @@ def test_one_pass_marching_cubes_equals_count_and_emit_passes(gpu_model):
     a = run(True)
     orig = M.DenseIndexedMap._extract_buffers
 
-    def without_status(self, *args, **kw):
+    def without_optional(self, *args, **kw):
         t, b = orig(self, *args, **kw)
-        b.mc_status = None                                   # dif_extract falls back to the count pass + emit pass
+        for name in withheld:                                # dif_extract falls back to the count pass (+ scan kernel) + emit pass
+            setattr(b, name, None)
         return t, b
 
-    M.DenseIndexedMap._extract_buffers = without_status
+    M.DenseIndexedMap._extract_buffers = without_optional
     try:
         b = run(False)
     finally:

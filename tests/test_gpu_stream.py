@@ -41,8 +41,8 @@ def test_eager_pipelined_and_direct_agree(gpu_model):
     per_frame = []
     for i in range(N_FRAMES):
         o = st.step(i, d2h="new")
+        torch.cuda.synchronize()                                 # (the copies into the pinned arrays are asynchronous)
         per_frame.append(tuple(x.clone() for x in o))
-    torch.cuda.synchronize()
     outs["eager"] = snapshot(st)
 
     st = make_stream(gpu_model)
@@ -246,7 +246,11 @@ def test_compaction_with_a_deferred_export_pending(other, gpu_model):
 def test_host_staging_overflow_falls_back(gpu_model):
     """A frame with more new triangles than its pinned staging slot holds must still hand back all of them (through the side-stream export)."""
     ref = make_stream(gpu_model)
-    want = [tuple(x.clone() for x in ref.step(i, d2h="new")) for i in range(4)]
+    want = []
+    for i in range(4):
+        o = ref.step(i, d2h="new")
+        torch.cuda.synchronize()                                 # (the copies into the pinned arrays are asynchronous)
+        want.append(tuple(x.clone() for x in o))
     st = make_stream(gpu_model)
     st.HOST_OUT_TRIANGLES = 64                               # instance attribute shadows the class default before the slots are made
     st.step(0, d2h="new")
@@ -614,6 +618,30 @@ def test_stream_group_argument_checks_and_mesh_left_in_hbm(gpu_model):
         fill(frames[1], b, tiled)
         assert lib.dif_integrate_frames(frames, 2, ctypes.byref(w), H, W, intr.fx, intr.fy, intr.cx, intr.cy, sp) == -1
         assert lib.dif_extract_streams(frames, 2, ctypes.byref(w), 5, 0.15, 1, sp) == -1                                      # resolution > 4
+        # everything else that takes an extract off the one chain the batched launches run, each on a copy of the descriptor it changes
+        extract = lambda wts=w: lib.dif_extract_streams(frames, 2, ctypes.byref(wts), 4, 0.15, 1, sp)
+        fill(frames[1], b)
+        for field in ("fold_table", "mc_status", "chunk_sum"):
+            buf = _lib.DifExtractBuffers.from_buffer_copy(b._d_bufs[0])
+            setattr(buf, field, None)
+            frames[1].buf = ctypes.pointer(buf)
+            assert extract() == -1, field
+        for field in ("dec_x6_packed", "dec_fold_packed"):
+            w2 = _lib.DifWeights.from_buffer_copy(w)
+            setattr(w2, field, None)
+            frames[1].buf = ctypes.pointer(b._d_bufs[0])
+            assert extract(w2) == -1, field
+        no_totals = _lib.DifMap.from_buffer_copy(b.map._cmap)
+        no_totals.dirty_tot = None                                               # no kept block totals of the dirty flags
+        fill(frames[1], b, no_totals)
+        assert extract() == -1
+        fewer = _lib.DifExtractBuffers.from_buffer_copy(b._d_bufs[0])
+        fewer.max_voxels = a._d_bufs[0].max_voxels - 1                           # the streams' extract rows differ
+        fill(frames[1], b)
+        frames[1].buf = ctypes.pointer(fewer)
+        assert extract() == -1
+        fill(frames[1], b)
+        assert extract() == 0                                                    # (the descriptors as the group left them: what the refusals above changed is why)
     with pytest.raises(ValueError):
         FusionStreamGroup([])
     torch.cuda.synchronize()
