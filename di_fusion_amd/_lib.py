@@ -95,6 +95,12 @@ class DifWeldArgs(ctypes.Structure):
     _fields_ = [("bound_min", c_float * 3), ("voxel_size", c_float), ("resolution", c_int32), ("n_xyz", c_int32 * 3)]
 
 
+class DifOptimizeViews(ctypes.Structure):
+    """include/difusion.h: dif_optimize_views_t"""
+    _fields_ = [("row_slot", c_void_p), ("row_xyz", c_void_p), ("row_sdf", c_void_p), ("uniq_slot", c_void_p), ("slot_u", c_void_p), ("slot_flag", c_void_p),
+                ("z", c_void_p), ("m", c_void_p), ("v", c_void_p)]
+
+
 WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 0, 1, 2, 3, 4, 8       # DIF_WELD_*
 
 SIGNATURES = {
@@ -163,6 +169,7 @@ SIGNATURES = {
     "dif_read_counters": (c_int32, [POINTER(DifMap), POINTER(c_int32), c_void_p]),
     "dif_test_mc_grid_cap": (c_int32, [c_int32]),
     "dif_test_sdma_mode": (c_int32, [c_int32]),
+    "dif_test_optimize_views": (c_int32, [c_int64, c_int64, c_void_p, POINTER(DifOptimizeViews)]),
     "dif_sdma_info": (c_int32, [POINTER(c_int32)]),
     "dif_test_handoff": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "dif_queues_independent": (c_int32, [c_void_p, c_void_p]),

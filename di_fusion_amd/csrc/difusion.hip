@@ -677,6 +677,16 @@ int64_t dif_optimize_workspace_bytes(int64_t N, int64_t capacity) {
     return ws.total_bytes;
 }
 
+int dif_test_optimize_views(int64_t N, int64_t capacity, void* wsp, dif_optimize_views_t* out) {
+    if (N <= 0 || capacity <= 0 || !wsp || !out) return DIF_EINVAL;
+    OptimWs ws;
+    carve_optimize(N, capacity, wsp, ws);
+    out->row_slot = ws.row_slot; out->row_xyz = ws.row_xyz; out->row_sdf = ws.row_sdf;
+    out->uniq_slot = ws.uniq_slot; out->slot_u = ws.slot_u; out->slot_flag = ws.slot_flag;
+    out->z = ws.z; out->m = ws.m; out->v = ws.v;
+    return DIF_OK;
+}
+
 int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const float* xyz, const float* normal, int64_t N, const uint8_t* unq_mask,
                          const float* noise, int32_t n_iters, float lr, float code_reg_lambda, float* loss_out, void* wsp, int64_t ws_bytes, void* stream_) {
     if (!map || !w || !map->voxel_optimized || N < 0 || n_iters < 0 || !(lr > 0.0f) || code_reg_lambda < 0.0f) return DIF_EINVAL;
@@ -716,7 +726,7 @@ int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const flo
         attr_set[dev] = true;
     }
     for (int it = 1; it <= n_iters; ++it) {
-        float* const loss_it = loss_out ? ws.loss + (it - 1 < 64 ? it - 1 : 63) : nullptr;
+        float* const loss_it = (loss_out && it <= 64) ? ws.loss + (it - 1) : nullptr;       // float[64]: the first 64 steps; later ones are not recorded
         if (x6)
             hipLaunchKernelGGL(k_optim_grad<true>, dim3(num_cus()), dim3(256), lds_bytes, s, (const float*)w->dec_x6_packed, (const float*)w->dec_x6b_packed,
                                (const float*)w->dec_x6u_packed, (const int*)ws.row_slot, (const float*)ws.row_xyz, (const float*)ws.row_sdf, (const int*)ws.slot_u,

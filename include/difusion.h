@@ -286,7 +286,8 @@ int dif_integrate_frame(const dif_map_t* map, const dif_weights_t* w, const dif_
  * over the perturbed surface samples gathered around them (8 offsets; row k is displaced along its normal by 0.05 * noise[k], rows in
  * the reference's gathering order: offset-major, then point order), then their latents are written back and they are marked optimised
  * and dirty.  noise: device, at least 8N floats of N(0,1) samples (the reference draws them from torch.randn).  loss_out: optional
- * device float[64], the likelihood part of the loss before each of the first 64 steps.  Counts -> DIF_C_OPT_ROWS / DIF_C_OPT_VOXELS.
+ * device float[64]: slot i holds the likelihood part of the loss (already divided by n_rows) at the latents BEFORE step i + 1, for the
+ * first min(n_iters, 64) steps; the remaining slots are zero and steps past the 64th are not recorded.  Counts -> DIF_C_OPT_ROWS / DIF_C_OPT_VOXELS.
  * Nothing synchronises. */
 int64_t dif_optimize_workspace_bytes(int64_t N, int64_t capacity);
 int dif_optimize_latents(const dif_map_t* map, const dif_weights_t* w, const float* xyz, const float* normal, int64_t N,
@@ -602,6 +603,16 @@ int dif_test_mc_grid_cap(int32_t n);
  * the runtime (what happens under a HIP runtime other than the validated one); 2 = fail with DIF_ELAUNCH (what happens when the process's HSA runtime
  * cannot be reached: the caller falls back to dif_mesh_cache_export_dma); 3 = count every export as slow (the engines are timed again after four). */
 int dif_test_sdma_mode(int32_t mode);
+/* TEST HOOK: the pointers dif_optimize_latents derives inside its workspace `ws` for this (N, capacity) — the gathered rows (row_slot[k], row_xyz[k][3],
+ * row_sdf[k] for k < DIF_C_OPT_ROWS), the optimised slots ascending (uniq_slot[u] for u < DIF_C_OPT_VOXELS) with their inverse slot_u[slot], the
+ * per-slot marks slot_flag[capacity] (all zero again when a call has finished), and the optimiser's state after the last step ([voxel u][32]
+ * floats each, channels 29..31 unused: latents z and Adam's moments m, v).  Launches nothing. */
+typedef struct dif_optimize_views {
+    int32_t* row_slot; float* row_xyz; float* row_sdf;
+    int32_t* uniq_slot; int32_t* slot_u; int32_t* slot_flag;
+    float* z; float* m; float* v;
+} dif_optimize_views_t;
+int dif_test_optimize_views(int64_t N, int64_t capacity, void* ws, dif_optimize_views_t* out);
 /* TEST HOOK: a litmus run of the fence-free hand-overs the product kernels use (write-through stores + s_waitcnt vmcnt(0) + word on the producer,
  * sc1 loads on the consumer; csrc/kernels_litmus.hip.h).  mode 0: `groups` workgroups meet `iters` times through a counter every one polls, each then
  * checks another workgroup's 29-double record (a launch-wide meeting: the pattern of profiles/r06_experiments.md 1); mode 1: the last arriver of a ticket checks all records

@@ -13,6 +13,7 @@ import numpy as np
 
 F64 = np.float64
 BN_EPS = 1e-5
+NLL_CLAMP = 0.2             # map.py:90-91: prediction and target are clamped to +-0.2 before the likelihood
 REFINE_TH = 0.05            # map.py:667: samples with |interpolated sdf| < 0.05 are decoded again
 
 
@@ -21,6 +22,26 @@ def softplus64(x):
     x = np.asarray(x, dtype=F64)
     with np.errstate(invalid="ignore"):
         return np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
+
+
+def code_reg_grad64(z, lam: float, n: int):
+    """d / dz of  lam * sum_voxels |z_u| / n  (map.py:98-101): lam * z / |z| / n, with the subgradient 0 at z = 0 (torch.norm's backward).
+    z (U,29) -> (U,29)."""
+    z = np.asarray(z, dtype=F64)
+    nrm = np.sqrt((z * z).sum(axis=1, keepdims=True))
+    return np.where(nrm > 0, lam * z / np.where(nrm > 0, nrm, 1.0) / n, 0.0)
+
+
+def adam_step64(z, m, v, g, it: int, lr=1e-2, b1=0.9, b2=0.999, eps=1e-8):
+    """Step `it` (1-based) of torch.optim.Adam with its defaults (no weight decay, no amsgrad) -> z, m, v."""
+    m = b1 * np.asarray(m, dtype=F64) + (1.0 - b1) * g
+    v = b2 * np.asarray(v, dtype=F64) + (1.0 - b2) * g * g
+    return adam_update64(z, m, v, it, lr, b1, b2, eps), m, v
+
+
+def adam_update64(z, m, v, it: int, lr=1e-2, b1=0.9, b2=0.999, eps=1e-8):
+    """The parameter update of that step from the moments it has just formed."""
+    return np.asarray(z, dtype=F64) - (lr / (1.0 - b1 ** it)) * (m / (np.sqrt(v) / np.sqrt(1.0 - b2 ** it) + eps))
 
 
 class Ref64:
@@ -77,6 +98,38 @@ class Ref64:
             gh = gin
         gx += gh[:, 29:]
         return sdf, 0.05 + 0.5 * softplus64(pu), gx
+
+    def decoder_nll_grad(self, x, gt, n):
+        """The optimiser's loss (map.py:87-96) and its gradient with respect to all 32 decoder inputs, per row:
+            loss_i = -log N(clamp(gt_i); clamp(sdf_i), std_i) / n        (clamps at +-0.2; torch.distributions.Normal.log_prob)
+        The clamp passes the gradient inside the CLOSED interval [-0.2, 0.2] (torch.clamp's backward); softplus' is the plain sigmoid (no
+        threshold: above 20 it differs from 1 by < 2.1e-9).
+        -> dict(loss (N,), grad (N,32), grad_abs (N,32): |sdf-head part| + |uncertainty-head part| of grad (the magnitude a relative error of
+        either upstream head acts on), grad_unc (N,32): the uncertainty-head part alone, sdf, std, ps, pu (N,), pre: the four hidden pre-activations)."""
+        h, pre = self._trunk(x)
+        gt = np.asarray(gt, dtype=F64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            ps = (h @ self.dec_W[4].T + self.dec_b[4])[:, 0]
+            pu = (h @ self.unc_W.T + self.unc_b)[:, 0]
+            sdf, std = np.tanh(ps), 0.05 + 0.5 * softplus64(pu)
+            diff = np.clip(gt, -NLL_CLAMP, NLL_CLAMP) - np.clip(sdf, -NLL_CLAMP, NLL_CLAMP)
+            var = std * std
+            loss = (np.log(std) + 0.5 * np.log(2.0 * np.pi) + diff * diff / (2.0 * var)) / n
+            d_mu = np.where((sdf >= -NLL_CLAMP) & (sdf <= NLL_CLAMP), -diff / var, 0.0)
+            d_sigma = 1.0 / std - diff * diff / (var * std)
+            a = d_mu * (1.0 - sdf * sdf) / n                                   # through tanh
+            b = d_sigma * 0.5 / (1.0 + np.exp(-pu)) / n                        # through 0.05 + 0.5 * softplus
+        N = h.shape[0]
+        gh = np.concatenate([a[:, None] * self.dec_W[4], b[:, None] * self.unc_W], axis=0)      # the two heads through one (linear) chain
+        gx = np.zeros((2 * N, 32), dtype=F64)
+        for layer in (3, 2, 1, 0):
+            gin = (gh * np.tile(pre[layer] > 0, (2, 1))) @ self.dec_W[layer]
+            if layer == 3:
+                gx += gin[:, 96:]                                                # the latent_in skip
+                gin = gin[:, :96]
+            gh = gin
+        gx += gh
+        return dict(loss=loss, grad=gx[:N] + gx[N:], grad_abs=np.abs(gx[:N]) + np.abs(gx[N:]), grad_unc=gx[N:], sdf=sdf, std=std, ps=ps, pu=pu, pre=pre)
 
     # ---- encoder ------------------------------------------------------------------------------------------------------------
     def encoder(self, x):

@@ -19,7 +19,7 @@ tanh, and the planted maps below carry latents of scale 4 and 16 into the map ke
   decoder_tile_grad_x6    test_point_queries[*-bf16x6]                        (k_decode_grad_x6)
   decoder_tile_folded     test_lattice_cubes[*-f32]                           (k_decode_voxels<false>, refine rows of k_decode)
   decoder_tile_folded_x6  test_lattice_cubes[*-bf16x6]                        (k_decode_voxels<true>, k_decode_refine_x6)
-  decoder_tile_nll_grad, decoder_tile_nll_grad_x6: the optimiser's tiles (k_optim_grad) are NOT covered here.
+  decoder_tile_nll_grad, decoder_tile_nll_grad_x6: the optimiser's tiles (k_optim_grad): tests/test_gpu_optim_envelope.py (its own per-tile table).
 The map tests assert on the float64 values that their planted latents reach pu > 20 and |sdf| > 0.999 (pu > 20: the hostile sets; with
 the shipped weights about one latent direction in a thousand has pu > 0, and only the explicit "pu(lo,hi]" rows get there).
 test_lattice_rounds walks the lattice kernel's round structure, test_sequence_on_foreign_weights the whole frame path with the hostile sets.

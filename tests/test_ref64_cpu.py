@@ -5,7 +5,10 @@
   * the analytic input gradient against float64 torch.autograd on a plain torch restatement;
   * that every weight set reaches every branch of the epilogue (softplus below 20, above 20, where expf would overflow; tanh in its
     linear part and saturated) on at least 1 % of the rows of some case;
-  * K of the GPU bar, re-measured (see mlp_cases.K_BAR).
+  * K of the GPU bar, re-measured (see mlp_cases.K_BAR), and K_NLL of the optimiser's gradient bar (optim_cases.K_NLL);
+  * the optimiser's loss and gradient (Ref64.decoder_nll_grad) against float64 autograd of the loss written with
+    torch.distributions.Normal(...).log_prob, the Adam step and the code regulariser against torch.optim.Adam in float64, and the NumPy
+    restatement of the optimiser's gather (optim_cases.gather_rows) against OracleMap._optimize_stage.
 
 `python tests/test_ref64_cpu.py` prints the table of profiles/mlp_envelope_k.md.
 """
@@ -19,6 +22,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from oracle import difusion_oracle as O  # noqa: E402
 from tests import mlp_cases as C  # noqa: E402
+from tests import optim_cases as OC  # noqa: E402
 from tests.ref64 import Ref64  # noqa: E402
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -135,6 +139,123 @@ def test_query_set_keeps_the_oracle_under_the_kink_cap(name):
         assert e <= 1e-4 * max(1.0, np.abs(g64[keep]).max()), (name, scale, e)
 
 
+# ---- the optimiser's loss, Adam, the regulariser -----------------------------------------------------------------------------------
+def _torch_nll(ref, x, gt, n, dtype):
+    """map.py:88-95 as torch writes it -> loss (scalar tensor), x (the leaf)"""
+    xt = torch.from_numpy(np.ascontiguousarray(x)).to(dtype).requires_grad_(True)
+    sdf, std = _torch_decoder(ref, xt, dtype)
+    gtc = torch.clamp(torch.from_numpy(np.ascontiguousarray(gt)).to(dtype), -0.2, 0.2)
+    ll = -torch.distributions.Normal(loc=torch.clamp(sdf, -0.2, 0.2), scale=std).log_prob(gtc)
+    return ll.sum() / n, xt
+
+
+def _nll_rows(name, s, n=1024, seed=9):
+    g = np.random.default_rng([seed, int(s * 10)])
+    return C.decoder_rows_scale(s, n, seed=seed), (0.05 * OC.planted_noise(g, n)).astype(F32)
+
+
+@pytest.mark.parametrize("name", C.WEIGHT_SETS)
+def test_nll_gradient_against_float64_autograd(name):
+    """Ref64.decoder_nll_grad against float64 autograd of the loss written with torch.distributions.Normal(...).log_prob: the loss, the
+    gradient with respect to all 32 inputs, and that its two parts add up to it.  (F.softplus in float64 has the `> 20` shortcut; it
+    differs from the plain sigmoid by < 2.1e-9 relative on the uncertainty head's part only.)"""
+    b = C.bundle(name)
+    for s in (0.3, 4.0, 16.0):
+        x, gt = _nll_rows(name, s)
+        n = x.shape[0]
+        r = b.ref.decoder_nll_grad(x, gt, n)
+        loss, xt = _torch_nll(b.ref, x, gt, n, torch.float64)
+        (tg,) = torch.autograd.grad(loss, xt)
+        tg = tg.numpy()
+        assert abs(r["loss"].sum() - loss.item()) <= 1e-12 * max(1.0, abs(loss.item()))
+        tol = 1e-11 * max(1e-300, np.abs(tg).max()) + 2.1e-9 * (r["pu"] > 20)[:, None] * r["grad_abs"]
+        assert (np.abs(r["grad"] - tg) <= tol).all(), (name, s, np.abs(r["grad"] - tg).max(), np.abs(tg).max())
+        assert (r["grad_abs"] >= np.abs(r["grad"]) * (1 - 1e-12)).all()
+        # the clamp passes the gradient on the closed interval: a row exactly at the clamp keeps its sdf-head part
+        assert ((np.abs(r["sdf"]) <= 0.2).mean() > 0) or s > 0.3
+
+
+def test_nll_gradient_closed_clamp_interval_and_target_clamp():
+    """|sdf| = 0.2 exactly passes the gradient (torch.clamp's backward is `min <= x <= max`), and a target beyond +-0.2 is clamped."""
+    x = torch.tensor([-0.2, 0.2, 0.2000001, -0.3], dtype=torch.float64, requires_grad=True)
+    torch.clamp(x, -0.2, 0.2).sum().backward()
+    assert x.grad.tolist() == [1.0, 1.0, 0.0, 0.0]
+    b = C.bundle("shipped")
+    x, gt = _nll_rows("shipped", 0.3, 64)
+    far = b.ref.decoder_nll_grad(x, np.full(64, 7.0), 64)
+    at = b.ref.decoder_nll_grad(x, np.full(64, 0.2), 64)
+    assert np.array_equal(far["grad"], at["grad"]) and np.array_equal(far["loss"], at["loss"])
+
+
+def test_adam_and_regulariser_against_torch_float64():
+    """Five steps of torch.optim.Adam (float64, defaults, lr 1e-2) on a quadratic plus the code regulariser written as the reference
+    writes it (map.py:98-99), against ref64.adam_step64 with code_reg_grad64; one all-zero latent, whose regulariser subgradient is 0
+    (torch.norm's backward) while the float32 oracle's z / |z| divides 0 by 0 there."""
+    from tests.ref64 import adam_step64, code_reg_grad64
+    g = np.random.default_rng(3)
+    z0 = g.standard_normal((7, 29))
+    z0[2] = 0.0
+    A, lam, n = g.standard_normal((29, 29)), 0.01, 13
+    zt = torch.from_numpy(z0.copy()).requires_grad_(True)
+    opt = torch.optim.Adam([zt], lr=1.0e-2)
+    z, m, v = z0.copy(), np.zeros_like(z0), np.zeros_like(z0)
+    for it in range(1, 6):
+        opt.zero_grad()
+        (((zt @ torch.from_numpy(A)) ** 2).sum() / n + lam * torch.sum(torch.norm(zt, dim=1)) / n).backward()
+        grad = 2.0 * ((z @ A) @ A.T) / n + code_reg_grad64(z, lam, n)
+        assert np.abs(grad - zt.grad.numpy()).max() <= 1e-13 * np.abs(grad).max()
+        if it == 1:
+            assert (code_reg_grad64(z, lam, n)[2] == 0).all() and np.isfinite(zt.grad.numpy()[2]).all()
+        opt.step()
+        z, m, v = adam_step64(z, m, v, grad, it)
+        assert np.abs(z - zt.detach().numpy()).max() <= 1e-13, it
+    with np.errstate(invalid="ignore", divide="ignore"):
+        zz = np.zeros((1, 29), dtype=F32)
+        assert np.isnan(F32(lam) * zz / np.sqrt((zz * zz).sum(axis=1, keepdims=True))).all()       # what OracleMap._optimize_stage evaluates there
+
+
+def test_gather_restatement_matches_the_oracle():
+    """optim_cases.gather_rows (points, normals, mask, map state -> rows) against OracleMap._optimize_stage's own gather on a map whose
+    state is planted the same way: the oracle's rows are recovered from the rows it hands to decoder_nll_grad."""
+    b = C.bundle("shipped")
+    case = OC.block_case("shipped", 0.3)
+    pm = case.pm
+    om = O.OracleMap(b.oracle, OC.BOUND_MIN, tuple(-v for v in OC.BOUND_MIN), OC.VOXEL)
+    om.allocate_block(pm.pos[:pm.n])
+    om.latent_vecs[:pm.n], om.voxel_obs_count[:pm.n], om.voxel_optimized[:pm.n] = pm.latent[:pm.n], pm.obs[:pm.n], pm.optimized[:pm.n].astype(bool)
+    om.optim_n_iters = 1
+    seen = {}
+    real = b.oracle.decoder_nll_grad
+    try:
+        b.oracle.decoder_nll_grad = lambda x, gt, n: (seen.update(x=x.copy(), gt=gt.copy(), n=n), real(x, gt, n))[1]
+        xn, lin = om.voxelize(case.xyz)
+        om._optimize_stage(xn, lin, case.normal, case.noise)
+    finally:
+        del b.oracle.decoder_nll_grad
+    assert seen["n"] == case.n_rows and np.array_equal(seen["gt"], case.row_sdf)
+    assert np.array_equal(seen["x"][:, 29:], case.row_xyz) and np.array_equal(seen["x"][:, :29], pm.latent[case.row_slot])
+    assert om.last_stats["optim_voxels"] == case.uniq.size
+    assert np.array_equal(np.nonzero(om.voxel_optimized)[0], np.union1d(case.uniq, np.nonzero(pm.optimized)[0]))
+    # and on the scene that meets every clause of the gather (mask-0 points are what the caller prunes: the oracle sees the others;
+    # NaN and out-of-grid points it cannot index, so they are left to the GPU test's restatement alone)
+    pm, xyz, nrm, mask, noise = OC.messy_scene(513, 1024, 0)
+    c = np.ceil(((xyz - pm.bound_min[None, :]) / F32(pm.voxel_size)).astype(F32))
+    ok = mask.astype(bool) & np.isfinite(xyz).all(axis=1) & (c >= 1).all(axis=1) & (c <= OC.GRID).all(axis=1)
+    om = O.OracleMap(b.oracle, OC.BOUND_MIN, tuple(-v for v in OC.BOUND_MIN), OC.VOXEL)
+    om.allocate_block(pm.pos[:pm.n])
+    om.latent_vecs[:pm.n], om.voxel_obs_count[:pm.n], om.voxel_optimized[:pm.n] = pm.latent[:pm.n], pm.obs[:pm.n], pm.optimized[:pm.n].astype(bool)
+    om.optim_n_iters = 1
+    try:
+        b.oracle.decoder_nll_grad = lambda x, gt, n: (seen.update(x=x.copy(), gt=gt.copy(), n=n), real(x, gt, n))[1]
+        xn, lin = om.voxelize(xyz[ok])
+        om._optimize_stage(xn, lin, nrm[ok], noise)
+    finally:
+        del b.oracle.decoder_nll_grad
+    slot, rxyz, rsdf = OC.gather_rows(pm, xyz, nrm, mask, noise)
+    assert seen["n"] == slot.size > 1000 and np.array_equal(seen["gt"], rsdf) and np.array_equal(seen["x"][:, 29:], rxyz)
+    assert np.array_equal(seen["x"][:, :29], pm.latent[slot]) and 0 not in pm.pos[slot]
+
+
 # ---- K ------------------------------------------------------------------------------------------------------------------------------
 def _seq_linear(h, W, b):
     """strict left-to-right float32 accumulation of h @ W.T, then + b"""
@@ -156,6 +277,48 @@ def _seq_decoder(on, x):
         h = np.maximum(_seq_linear(h, on.dec_W[layer], on.dec_b[layer]), F32(0))
     std = (F32(0.05) + F32(0.5) * O._softplus(_seq_linear(h, on.unc_W, on.unc_b))).astype(F32)
     return np.tanh(_seq_linear(h, on.dec_W[4], on.dec_b[4])).astype(F32)[:, 0], std[:, 0]
+
+
+def _seq_nll_sums(case):
+    """OracleNetworks.decoder_nll_grad's arithmetic with every matrix product accumulated strictly left to right, per-voxel sums in row order"""
+    import math
+    on, x0, n = case.b.oracle, case.rows_at(case.pm.latent[case.uniq]).astype(F32), case.n_rows
+    h, masks = x0, []
+    for layer in range(4):
+        if layer == 3:
+            h = np.concatenate([h, x0], axis=1)
+        h = _seq_linear(h, on.dec_W[layer], on.dec_b[layer])
+        masks.append(h > 0)
+        h = np.maximum(h, F32(0))
+    ps, pu = _seq_linear(h, on.dec_W[4], on.dec_b[4])[:, 0], _seq_linear(h, on.unc_W, on.unc_b)[:, 0]
+    mu, sigma = np.tanh(ps).astype(F32), (F32(0.05) + F32(0.5) * O._softplus(pu)).astype(F32)
+    diff = (np.clip(case.row_sdf, F32(-0.2), F32(0.2)) - np.clip(mu, F32(-0.2), F32(0.2))).astype(F32)
+    inv_n = F32(1.0 / n)
+    d_mu = (-diff / (sigma * sigma) * ((mu >= F32(-0.2)) & (mu <= F32(0.2)))).astype(F32)
+    d_sigma = (F32(1) / sigma - diff * diff / (sigma * sigma * sigma)).astype(F32)
+    a = (inv_n * d_mu * (F32(1) - mu * mu)).astype(F32)
+    with np.errstate(over="ignore"):
+        bb = (inv_n * d_sigma * F32(0.5) * np.where(pu > F32(20), F32(1), F32(1) / (F32(1) + np.exp(-pu)))).astype(F32)
+    gh = (a[:, None] * on.dec_W[4] + bb[:, None] * on.unc_W).astype(F32)
+    gx = np.zeros_like(x0)
+    for layer in (3, 2, 1, 0):
+        gin = _seq_linear((gh * masks[layer]).astype(F32), np.ascontiguousarray(on.dec_W[layer].T), F32(0))
+        if layer == 3:
+            gx += gin[:, 96:]
+            gin = gin[:, :96]
+        gh = gin
+    gx += gh
+    return case.sums(gx[:, :29].astype(F32))
+
+
+def _torch_nll_sums(case, ref32):
+    """torch float32 autograd of the loss with respect to the per-voxel latents (the gather's backward adds the rows up)"""
+    z = torch.from_numpy(case.pm.latent[case.uniq].copy()).requires_grad_(True)
+    x = torch.cat([z[torch.from_numpy(case.inv)], torch.from_numpy(case.row_xyz)], dim=1)
+    sdf, std = _torch_decoder(ref32, x, torch.float32)
+    ll = -torch.distributions.Normal(loc=torch.clamp(sdf, -0.2, 0.2), scale=std).log_prob(torch.clamp(torch.from_numpy(case.row_sdf), -0.2, 0.2))
+    (g,) = torch.autograd.grad(ll.sum() / case.n_rows, z)
+    return g.numpy()
 
 
 def _encoder_f32(on, x, linear):
@@ -201,6 +364,14 @@ def _k_rows(b):
         assert (~keep).mean() <= 0.01, (name, s, (~keep).mean())
         e = [C.max_err(b.oracle.decoder_xyz_grad(x)[2][keep], g64[keep]), C.max_err(_torch_grad(ref32, x, torch.float32)[1][keep], g64[keep])]
         rows.append((name, "gradient", f"N(0,{s:g})", "d sdf / d xyz", e, max(e) / min(e)))
+    # the optimiser's per-voxel gradient sums, on the very cases tests/test_gpu_optim_envelope.py runs (their points are filtered already)
+    for ws, s in OC.ONE_STEP + [(w, OC.NEAR_SWITCH) for w in C.WEIGHT_SETS] + [("large_pu", 0.0)]:
+        if name != (ws if ws != "large_pu" else "shipped"):
+            continue
+        case = OC.one_step_case(ws, s)
+        g64 = case.grad64()["G"]
+        e = [C.max_err(case.grad32()[0], g64), C.max_err(_torch_nll_sums(case, ref32), g64), C.max_err(_seq_nll_sums(case), g64)]
+        rows.append((name, "nll gradient", case.label.split("/")[1], "d loss / d z per voxel", e, max(e) / min(e)))
     return rows
 
 
@@ -208,6 +379,12 @@ def test_k_of_the_bar():
     """K_BAR is twice the largest ratio between honest float32 evaluations: re-measured here, and not more than twice that again (a K
     that has drifted far above the measurement protects nothing)."""
     rows = k_table()
+    nll = [r for r in rows if r[1] == "nll gradient"]
+    rows = [r for r in rows if r[1] != "nll gradient"]
+    worst_nll = max(r[5] for r in nll)
+    print(f"nll gradient: largest ratio {worst_nll:.2f} over {len(nll)} cases; K_NLL = {OC.K_NLL}")
+    for r in nll:
+        print(f"  {r[0]} / {r[2]}: {r[5]:.2f}  errors {['%.3g' % e for e in r[4]]}")
     worst = max(r[5] for r in rows)
     print(f"largest ratio {worst:.2f} over {len(rows)} (weight set, case, output) triples; K_BAR = {C.K_BAR}")
     for net in ("decoder", "encoder", "gradient"):
@@ -216,6 +393,7 @@ def test_k_of_the_bar():
     # 10 % of slack on the upper side: the ratios depend on the BLAS build's summation order (3.19 where K_BAR was set); past that, or
     # below half of it, the constant no longer describes the measurement and has to be derived again
     assert C.K_BAR / 4.0 <= worst <= 1.1 * C.K_BAR / 2.0, worst
+    assert OC.K_NLL / 4.0 <= worst_nll <= 1.1 * OC.K_NLL / 2.0, worst_nll
 
 
 if __name__ == "__main__":
@@ -228,7 +406,7 @@ if __name__ == "__main__":
         print("|---|---|---|---|---|---|---|---|")
         best = {}
         for r in rows:
-            key = (r[0], r[1], r[3] if r[1] == "decoder" else "")
+            key = (r[0], r[1], r[3] if r[1] == "decoder" else r[2] if r[1] == "nll gradient" else "")
             if key not in best or r[5] > best[key][5]:
                 best[key] = r
         rows = list(best.values())
