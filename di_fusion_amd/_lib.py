@@ -101,6 +101,11 @@ class DifOptimizeViews(ctypes.Structure):
                 ("z", c_void_p), ("m", c_void_p), ("v", c_void_p)]
 
 
+class DifIntegrateViews(ctypes.Structure):
+    """include/difusion.h: dif_integrate_views_t"""
+    _fields_ = [("pt_lin", c_void_p), ("pair_list", c_void_p), ("rec_next", c_void_p), ("rec", c_void_p)]
+
+
 WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 0, 1, 2, 3, 4, 8       # DIF_WELD_*
 
 SIGNATURES = {
@@ -170,6 +175,7 @@ SIGNATURES = {
     "dif_test_mc_grid_cap": (c_int32, [c_int32]),
     "dif_test_sdma_mode": (c_int32, [c_int32]),
     "dif_test_optimize_views": (c_int32, [c_int64, c_int64, c_void_p, POINTER(DifOptimizeViews)]),
+    "dif_test_integrate_views": (c_int32, [c_int64, c_void_p, POINTER(DifIntegrateViews)]),
     "dif_sdma_info": (c_int32, [POINTER(c_int32)]),
     "dif_test_handoff": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "dif_queues_independent": (c_int32, [c_void_p, c_void_p]),

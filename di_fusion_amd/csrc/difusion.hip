@@ -441,6 +441,14 @@ int64_t dif_integrate_workspace_bytes(int64_t N) {
     return ws.total_bytes;
 }
 
+int dif_test_integrate_views(int64_t N, void* wsp, dif_integrate_views_t* out) {
+    if (N <= 0 || !wsp || !out) return DIF_EINVAL;
+    IntegrateWs ws;
+    if (carve_integrate(N, wsp, ws) != DIF_OK) return DIF_ELAUNCH;
+    out->pt_lin = ws.pt_lin; out->pair_list = (uint32_t*)ws.pair_list; out->rec_next = ws.rec_next; out->rec = (int64_t*)ws.rec;
+    return DIF_OK;
+}
+
 struct FrameSource {            // integrate straight from a depth frame: the first kernel also produces xyz / normal
     const dif_frame_t* frame;
     int H, W;

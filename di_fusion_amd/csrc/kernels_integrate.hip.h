@@ -391,6 +391,14 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_focus_gather_batch(Batch<GatherAr
 #define DIF_REC_COUNT_POS 29                 /* record position that carries the run length (feature 29 is a zero row of the MFMA tile) */
 #define DIF_DIR_WORDS 16                     /* int32 per slot directory: count | overflow chain head | 14 record ids */
 #define DIF_DIR_IDS (DIF_DIR_WORDS - 2)
+// NON-FINITE INPUTS.  A point whose position is finite and whose normal holds a NaN or an infinity passes every stage in front of the
+// encoder (those look at the position only).  The reference's float arithmetic makes NaN of such a row, hence of the latent of every
+// voxel the row feeds (up to eight); computed here, relu1's integer max and the conversion to fixed point would turn it into zeros,
+// saturated or arbitrary finite numbers.  So, as in k_encode_rows, the row is flagged where its inputs are gathered: every flagged row
+// adds 2^40 to the run length in record position 29 (a run holds at most 32 rows, a voxel fewer than 2^21), and k_fuse, which splits the
+// word, stores NaN in every channel of a voxel with a flagged row.  Counts, dirty flags and all other voxels are what they would be
+// with a finite normal.
+#define DIF_REC_POISON_SHIFT 40
 
 #ifdef DIF_TRACE            // tools/trace_decode.py --encode: per-wave phase timestamps (100 MHz wall clock) of the last k_encode launch
 __device__ unsigned long long g_en_trace[4096 * 8];       // (up to 16 waves x 256 workgroups; the x6 kernel runs 12 waves per workgroup)
@@ -492,6 +500,10 @@ __device__ __forceinline__ void encode_body(const BatchN<EncArgs, NS>& B, int S,
         const int my_head = 31 - __clz((int)(heads32 & ((2u << col) - 1u)));      // column where this lane's run starts
         const int rec_id = tile * 32 + __popc(heads32 & ((2u << col) - 1u)) - 1;  // record of this lane's run
         const float x0 = cur.x0, x1 = cur.x1, x2 = cur.x2;
+        // a row that holds a NaN or an infinity (see NON-FINITE INPUTS above): flag taken here, from the two halves' three inputs each
+        unsigned nf = (((__float_as_uint(x0) & 0x7f800000u) == 0x7f800000u) || ((__float_as_uint(x1) & 0x7f800000u) == 0x7f800000u) ||
+                       ((__float_as_uint(x2) & 0x7f800000u) == 0x7f800000u)) ? 1u : 0u;
+        nf |= (unsigned)__shfl_xor((int)nf, 32);
         // enter the run in its slot's directory.  Asked after the gathers above have been consumed and before the MFMA chain, answered
         // after it: the round trip hides behind ~11 us of matrix work.
         EN_STAMP(2);
@@ -507,7 +519,7 @@ __device__ __forceinline__ void encode_body(const BatchN<EncArgs, NS>& B, int S,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             long long v = live ? __float2ll_rn(out[r] * DIF_FIX_SCALE) : 0ll;
-            if (half == 1 && r == 13) v = live ? 1ll : 0ll;          // feature 29 (a zero row): carries the run length instead
+            if (half == 1 && r == 13) v = live ? 1ll + ((long long)nf << DIF_REC_POISON_SHIFT) : 0ll;      // feature 29 (a zero row): carries the run length (and its flagged rows) instead
             v = seg_incl_scan32(v, col, my_head);            // sum of the lane's run up to its column
             if (live && run_tail) p[r] = v;
         }
@@ -607,25 +619,28 @@ __device__ __forceinline__ void fuse_body(const long long* __restrict__ rec, con
         const float w_old = obs[s];                                               // (requested beside the directory, not behind the records)
         const float z_old = f < L ? latent[(int64_t)s * L + f] : 0.0f;
         long long Si = 0;
-        int cnt = 0;
+        long long len = 0;                                      // run lengths in the low DIF_REC_POISON_SHIFT bits, flagged rows above them
         const int n_dir = n_rec < DIF_DIR_IDS ? n_rec : DIF_DIR_IDS;
         for (int j = 0; j < n_dir; ++j) {                       // independent loads: all in flight together
             const long long* r = rec + (int64_t)__shfl(my_id, j, 32) * DIF_REC_WORDS;
             Si += r[pos];
-            cnt += (int)r[DIF_REC_COUNT_POS];
+            len += r[DIF_REC_COUNT_POS];
         }
         if (n_rec > DIF_DIR_IDS)
             for (int id = dir[1]; id != 0; id = rec_next[id - 1]) {
                 const long long* r = rec + (int64_t)(id - 1) * DIF_REC_WORDS;
                 Si += r[pos];
-                cnt += (int)r[DIF_REC_COUNT_POS];
+                len += r[DIF_REC_COUNT_POS];
             }
+        const int cnt = (int)(len & ((1ll << DIF_REC_POISON_SHIFT) - 1));
         if (f < L) {
             float S = (float)Si * (1.0f / DIF_FIX_SCALE);    // one rounding: exact integer sum -> nearest float
             S = S + z_old * w_old;                           // map.py:449
             float w_new = w_old + (float)cnt;                // map.py:450
-            latent[(int64_t)s * L + f] = S / w_new;          // map.py:451
+            // (a row with a non-finite input poisons its voxel, as the reference's float arithmetic does: NON-FINITE INPUTS above)
+            latent[(int64_t)s * L + f] = (len >> DIF_REC_POISON_SHIFT) ? __builtin_nanf("") : S / w_new;          // map.py:451
         }
+        if (my_id >= 0) dir[2 + f] = 0;                      // the directory goes back to idle: all zero
         __builtin_amdgcn_wave_barrier();
         if (f == 31) {                                       // after every lane of the group has read obs[s]
             obs[s] = w_old + (float)cnt;

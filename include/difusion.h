@@ -613,6 +613,14 @@ typedef struct dif_optimize_views {
     float* z; float* m; float* v;
 } dif_optimize_views_t;
 int dif_test_optimize_views(int64_t N, int64_t capacity, void* ws, dif_optimize_views_t* out);
+/* TEST HOOK: the pointers dif_integrate / dif_integrate_frame derive inside their workspace `ws` for N points, all of which survive the call —
+ * pt_lin[N] (a point's linear voxel id, -1: NaN or outside the grid), pair_list[k][2] for k < DIF_C_M (slot, offset * N + point), the run records
+ * rec[id][32] (int64, 2^-30 fixed point; position 29 holds the run's length; id = tile * 32 + the run's rank in its tile of 32 list entries) and
+ * their chain links rec_next[id].  The record directory and the update list are the map's own buffers.  Launches nothing. */
+typedef struct dif_integrate_views {
+    int32_t* pt_lin; uint32_t* pair_list; int32_t* rec_next; int64_t* rec;
+} dif_integrate_views_t;
+int dif_test_integrate_views(int64_t N, void* ws, dif_integrate_views_t* out);
 /* TEST HOOK: a litmus run of the fence-free hand-overs the product kernels use (write-through stores + s_waitcnt vmcnt(0) + word on the producer,
  * sc1 loads on the consumer; csrc/kernels_litmus.hip.h).  mode 0: `groups` workgroups meet `iters` times through a counter every one polls, each then
  * checks another workgroup's 29-double record (a launch-wide meeting: the pattern of profiles/r06_experiments.md 1); mode 1: the last arriver of a ticket checks all records

@@ -51,14 +51,15 @@ def nll_bar(e_ref: float, rows_u, G64, S, k=None):
 
 # ---- planted maps ---------------------------------------------------------------------------------------------------------------
 class Planted:
-    """The state of a 16^3 map with the voxels `lin` allocated in ascending id order (allocate_block, map.py:310-319), as NumPy arrays."""
+    """The state of a grid^3 map (16^3 unless said otherwise) with the voxels `lin` allocated in ascending id order (allocate_block,
+    map.py:310-319), as NumPy arrays."""
 
-    def __init__(self, lin, capacity: int, latents=None, obs=None, optimized=None):
+    def __init__(self, lin, capacity: int, latents=None, obs=None, optimized=None, grid: int = GRID, voxel: float = VOXEL):
         lin = np.sort(np.asarray(lin, dtype=np.int64))
         assert np.unique(lin).size == lin.size and lin.size <= capacity
-        self.n, self.capacity = int(lin.size), int(capacity)
-        self.bound_min, self.voxel_size = np.asarray(BOUND_MIN, dtype=F32), VOXEL
-        self.indexer = -np.ones(GRID ** 3, dtype=np.int64)
+        self.n, self.capacity, self.grid = int(lin.size), int(capacity), int(grid)
+        self.bound_min, self.voxel_size = np.asarray(BOUND_MIN, dtype=F32), voxel
+        self.indexer = -np.ones(self.grid ** 3, dtype=np.int64)
         self.indexer[lin] = np.arange(self.n)
         self.pos = -np.ones(capacity, dtype=np.int64)
         self.pos[:self.n] = lin
@@ -76,34 +77,36 @@ class Planted:
         return (self.obs >= F32(ENC_TH)) & (self.optimized == 0) & (self.pos > 0)
 
     def slot_of(self, ijk):
-        ijk = np.asarray(ijk, dtype=np.int64)
-        return self.indexer[ijk[..., 2] + GRID * ijk[..., 1] + GRID * GRID * ijk[..., 0]]
+        return self.indexer[lin_of(ijk, self.grid)]
 
 
-def lin_of(ijk):
+def lin_of(ijk, grid: int = GRID):
     ijk = np.asarray(ijk, dtype=np.int64)
-    return ijk[..., 2] + GRID * ijk[..., 1] + GRID * GRID * ijk[..., 0]
+    return ijk[..., 2] + grid * ijk[..., 1] + grid * grid * ijk[..., 0]
 
 
-def points_in(ijk, frac):
+def points_in(ijk, frac, voxel: float = VOXEL):
     """World points at fraction `frac` (in (0, 1]) of voxels `ijk` -> float32 (N,3)"""
-    return ((np.asarray(ijk, dtype=np.float64) + frac) * VOXEL + np.asarray(BOUND_MIN, dtype=np.float64)).astype(F32)
+    return ((np.asarray(ijk, dtype=np.float64) + frac) * voxel + np.asarray(BOUND_MIN, dtype=np.float64)).astype(F32)
 
 
 # ---- the gather (map.py:459-497), restated with the oracle's float32 operations ------------------------------------------------------
 OFFSETS = np.array([[(-0.5, 0.5)[(o >> 2) & 1], (-0.5, 0.5)[(o >> 1) & 1], (-0.5, 0.5)[o & 1]] for o in range(8)], dtype=F32)      # map.py:186-189
 
 
-def gather_pairs(pm: Planted, xyz, mask):
+def gather_pairs(pm: Planted, xyz, mask, in_set=None):
     """The (offset, point) pairs that become rows, in the reference's order (offset-major, then point order)
-    -> o (R,), i (R,), slot (R,) int64, rel (R,3) float32 (the unperturbed position relative to the row's voxel)."""
+    -> o (R,), i (R,), slot (R,) int64, rel (R,3) float32 (the unperturbed position relative to the row's voxel).
+    in_set (capacity,) bool: the slots that take rows — the optimiser's set (pm.in_set(), map.py:465-467) unless given; integrate's gather
+    (map.py:389-433) is the same walk over its encode set {obs < encoder_count_th} (tests/integrate_cases.py)."""
+    GRID = pm.grid
     xyz = np.asarray(xyz, dtype=F32)
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         xn = ((xyz - pm.bound_min[None, :]) / F32(pm.voxel_size)).astype(F32)            # map.py:366-367
         c = np.ceil(xn)
         ok = np.asarray(mask).astype(bool) & (c >= 1).all(axis=1) & (c <= GRID).all(axis=1)      # NaN fails every comparison
-    gid = np.where(ok[:, None], c - 1, 0).astype(np.int64)
-    in_set = pm.in_set()
+        gid = np.where(ok[:, None], c - 1, 0).astype(np.int64)
+    in_set = pm.in_set() if in_set is None else np.asarray(in_set, dtype=bool)
     status = np.zeros(GRID ** 3, dtype=bool)
     status[pm.pos[in_set]] = True
     # get_pruned_surface (map.py:389-399): the point's own voxel or one of its six neighbours, clamped to the grid, is in the set
@@ -113,15 +116,15 @@ def gather_pairs(pm: Planted, xyz, mask):
         for s in (-1, 1):
             q = ijk.copy()
             q[:, d] = np.clip(q[:, d] + s, 0, GRID - 1)
-            exp[lin_of(q)] = True
-    focus = ok & exp[lin_of(gid)]
+            exp[lin_of(q, GRID)] = True
+    focus = ok & exp[lin_of(gid, GRID)]
     idx = np.nonzero(focus)[0]
     pxn = xn[idx]
     o_all, i_all, s_all, r_all = [], [], [], []
     for o, off in enumerate(OFFSETS):                                                    # map.py:479-493
         g = np.clip(np.ceil((pxn + off[None, :]).astype(F32)) - F32(1), 0, GRID - 1).astype(F32)
         rel = ((pxn - g).astype(F32) - F32(0.5)).astype(F32)
-        lin = lin_of(g.astype(np.int64))
+        lin = lin_of(g.astype(np.int64), GRID)
         m = status[lin]
         o_all.append(np.full(int(m.sum()), o, dtype=np.int64))
         i_all.append(idx[m])

@@ -8,7 +8,9 @@
   * K of the GPU bar, re-measured (see mlp_cases.K_BAR), and K_NLL of the optimiser's gradient bar (optim_cases.K_NLL);
   * the optimiser's loss and gradient (Ref64.decoder_nll_grad) against float64 autograd of the loss written with
     torch.distributions.Normal(...).log_prob, the Adam step and the code regulariser against torch.optim.Adam in float64, and the NumPy
-    restatement of the optimiser's gather (optim_cases.gather_rows) against OracleMap._optimize_stage.
+    restatement of the optimiser's gather (optim_cases.gather_rows) against OracleMap._optimize_stage;
+  * the NumPy restatement of the integrate chain (integrate_cases.restate, fuse32) against OracleMap.integrate_keyframe on the cases of
+    tests/test_gpu_integrate_envelope.py, and that those cases reach the paths they are there for.
 
 `python tests/test_ref64_cpu.py` prints the table of profiles/mlp_envelope_k.md.
 """
@@ -254,6 +256,116 @@ def test_gather_restatement_matches_the_oracle():
     slot, rxyz, rsdf = OC.gather_rows(pm, xyz, nrm, mask, noise)
     assert seen["n"] == slot.size > 1000 and np.array_equal(seen["gt"], rsdf) and np.array_equal(seen["x"][:, 29:], rxyz)
     assert np.array_equal(seen["x"][:, :29], pm.latent[slot]) and 0 not in pm.pos[slot]
+
+
+# ---- the integrate chain's restatement (tests/integrate_cases.py) -------------------------------------------------------------------
+def _integrate_cases():
+    from tests import integrate_cases as IC
+    return IC, [IC.faces_case(n, p) for n in IC.FACES_N for p in (0, 1)] + [IC.runs_case(4), IC.runs_case(0), IC.corners_case(), IC.alloc64_case(),
+                                                                             IC.threshold_case(), IC.chain_case(n_frames=3), IC.frame_case(32, 48), IC.frame_case(24, 40)]
+
+
+def test_integrate_restatement_matches_the_oracle():
+    """integrate_cases.restate against OracleMap.integrate_keyframe on every case the oracle can take (all but the capacity overflow; NaN
+    and out-of-grid points, invalid in both, are taken out of the oracle's cloud: it would index with them): mask, indexer, positions,
+    counts, n_occupied, M, C and the update set bit for bit over all frames; latents, fused by fuse32 from the oracle's own float32
+    encoder rows, to the oracle's rounding: its float32 running sum of cnt rows is off by at most cnt ulp of the sum of magnitudes, the
+    fixed point by half a unit per row, and three more roundings follow."""
+    IC, cases = _integrate_cases()
+    _, oracle = IC.nets("shipped")
+    for case in cases:
+        pm = case.pm.clone()
+        hi = tuple(float(v) + pm.grid * pm.voxel_size for v in OC.BOUND_MIN)
+        om = O.OracleMap(oracle, OC.BOUND_MIN, hi, pm.voxel_size, prune_min_vox_obs=case.prune_min, encoder_count_th=IC.TH)
+        assert om.n_xyz == [pm.grid] * 3, (case.label, om.n_xyz)
+        om.allocate_block(pm.pos[:pm.n])
+        om.latent_vecs[:pm.n], om.voxel_obs_count[:pm.n] = pm.latent[:pm.n], pm.obs[:pm.n]
+        for f, (xyz, nrm) in enumerate(case.frames):
+            label = f"{case.label} frame {f}"
+            k = min(pm.capacity, om.latent_vecs.shape[0])
+            pm.latent[:k] = om.latent_vecs[:k]                       # every frame is judged from the oracle's own previous latents
+            z_old = pm.latent.copy()
+            r = IC.restate(pm, xyz, nrm, case.prune_min)
+            ok = r.pt_lin >= 0
+            omask = om.integrate_keyframe(xyz[ok], nrm[ok])
+            mask = np.zeros(r.N, dtype=np.uint8)
+            mask[ok] = 1 if omask is None else omask
+            assert np.array_equal(mask, r.mask), label
+            assert om.n_occupied == pm.n and np.array_equal(om.indexer, pm.indexer) and np.array_equal(om.latent_vecs_pos[:pm.n], pm.pos[:pm.n]), label
+            assert np.array_equal(om.voxel_obs_count[:pm.n].view(np.uint32), pm.obs[:pm.n].view(np.uint32)), label
+            assert om.last_stats["M"] == r.M and om.last_stats["C"] == r.C, (label, om.last_stats, r.M, r.C)
+            assert np.array_equal(np.nonzero(pm.dirty)[0], om.updated_vec_id), label
+            if r.M:
+                assert not IC.nonfinite_rows(r.rows).any(), label
+                enc = oracle.encoder(r.rows)
+                z_new, w_new = IC.fuse32(z_old[r.uniq], r.w_old[r.uniq], IC.fixed_sums(r, enc), r.cnt)
+                pm.latent[r.uniq] = z_new
+                assert np.array_equal(w_new.view(np.uint32), pm.obs[r.uniq].view(np.uint32)), label
+                mag = np.zeros((r.C, 29))
+                np.add.at(mag, r.inv, np.abs(enc.astype(np.float64)))
+                with np.errstate(invalid="ignore"):
+                    mag = (mag + np.abs(z_old[r.uniq].astype(np.float64)) * r.w_old[r.uniq][:, None]) / w_new[:, None]
+                tol = (r.cnt[:, None] + 3.0) * 2.0 ** -24 * mag + r.cnt[:, None] * 2.0 ** -31 / w_new[:, None]
+                err = np.abs(om.latent_vecs[r.uniq].astype(np.float64) - z_new)
+                assert (err <= tol).all(), (label, float(np.nanmax(err / tol)))
+            rest = np.ones(pm.capacity, dtype=bool)
+            rest[r.uniq] = False
+            rest[om.latent_vecs.shape[0]:] = False
+            assert np.array_equal(om.latent_vecs[rest[:om.latent_vecs.shape[0]]].view(np.uint32), pm.latent[rest].view(np.uint32)), label
+
+
+def test_integrate_cases_reach_their_paths():
+    """What each case is there for, asserted from the restatement alone (the GPU test asserts the same from what it reads back): the
+    chain case's slots with more run records than a directory holds (14) beside slots with fewer, a workgroup with more distinct slots
+    than k_focus_gather's 256-entry table, alloc64's new voxels in at least three scan blocks, the overflow case 8 short, the frame
+    cases on either walk with holes, zeros and kept points, exact voxel faces among the faces case's points, and the thresholds."""
+    IC, _ = _integrate_cases()
+    c = IC.chain_case(n_frames=1)
+    pm = c.pm.clone()
+    r = IC.restate(pm, *c.frames[0], c.prune_min)
+    got = IC.reach(r)
+    block = pm.indexer[OC.lin_of(np.stack(np.meshgrid(*[np.arange(6, 9)] * 3, indexing="ij"), axis=-1).reshape(-1, 3))]
+    own = np.unique(np.stack([IC.workgroup_of(r.key, r.N), r.slot], axis=1)[np.isin(r.slot, block)], axis=0)
+    assert np.bincount(own[:, 1])[block].min() >= 29, np.bincount(own[:, 1])[block].min()
+    assert got["max_runs"] > IC.DIR_IDS and got["min_runs"] <= IC.DIR_IDS and got["max_slots_per_wg"] > 256, got
+    assert r.M < 8 * r.N and r.M % 32 != 0                                   # a partly filled last tile
+    c = IC.alloc64_case()
+    pm = c.pm.clone()
+    r = IC.restate(pm, *c.frames[0], c.prune_min)
+    assert 280 <= r.alloc_new <= 330 and np.unique(r.candidates // 32 // 256).size >= 3 and r.n_before == 40, (r.alloc_new, r.n_before)
+    assert pm.grid ** 3 // 32 > 4096
+    c = IC.overflow_case()
+    pm = c.pm.clone()
+    r = IC.restate(pm, *c.frames[0], c.prune_min)
+    assert r.overflow == 1 and pm.n == pm.capacity == r.n_before + r.alloc_new - 8 and (pm.indexer[r.candidates[-8:]] == -1).all()
+    for hw in ((32, 48), (24, 40)):
+        c = IC.frame_case(*hw)
+        r = IC.restate(c.pm.clone(), *c.frames[0], c.prune_min)
+        assert np.isnan(c.depth).sum() > 20 and (c.depth == 0).sum() > 5 and r.mask.sum() > r.N // 2 and r.M > 1000 and r.alloc_new > 20, (hw, r.M)
+        assert (r.pt_lin < 0).sum() == np.isnan(c.depth).sum()
+    c = IC.faces_case(257, 0)
+    xyz = c.frames[0][0]
+    with np.errstate(invalid="ignore"):
+        xn = ((xyz - np.asarray(OC.BOUND_MIN, dtype=F32)) / F32(OC.VOXEL)).astype(F32)
+    on_face = np.isfinite(xn) & (xn == np.round(xn))
+    lin = IC.voxel_ids(c.pm, xyz)
+    assert on_face.any(axis=1).sum() >= 20 and (xn == 0).any() and (xn == 16).any() and (lin < 0).sum() >= 20 and (lin >= 0).sum() >= 150
+    top = (np.asarray(OC.BOUND_MIN, dtype=np.float64) + 16 * OC.VOXEL).astype(F32)
+    assert IC.voxel_ids(c.pm, top[None, :])[0] == 16 ** 3 - 1 and IC.voxel_ids(c.pm, np.asarray(OC.BOUND_MIN, dtype=F32)[None, :])[0] == -1
+    c = IC.threshold_case()
+    pm = c.pm.clone()
+    s = lambda v: pm.indexer[OC.lin_of(v)]
+    r0 = IC.restate(pm, *c.frames[0], c.prune_min)
+    assert s([4, 4, 4]) in r0.uniq and s([4, 4, 5]) not in r0.uniq and s([4, 4, 6]) not in r0.uniq          # th - 1 in; th + 1 and th out
+    assert pm.obs[s([4, 4, 4])] >= IC.TH
+    from_outside = r0.pt_lin[r0.i] == OC.lin_of([4, 4, 5])                       # points of the th + 1 voxel: focus passed, rows go to th - 1 alone
+    assert from_outside.any() and (r0.slot[from_outside] == s([4, 4, 4])).all()
+    r1 = IC.restate(pm, *c.frames[1], c.prune_min)
+    assert s([4, 4, 4]) not in r1.uniq and s([13, 13, 2]) in r1.uniq
+    c = IC.runs_case(4)
+    r = IC.restate(c.pm.clone(), *c.frames[0], c.prune_min)
+    cnt = np.bincount(r.pt_lin[r.pt_lin >= 0], minlength=4096)
+    assert not r.mask[cnt[r.pt_lin] == 4].any() and r.mask[cnt[r.pt_lin] == 5].all() and (cnt[r.pt_lin] == 4).sum() == 8
 
 
 # ---- K ------------------------------------------------------------------------------------------------------------------------------
