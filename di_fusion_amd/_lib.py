@@ -107,6 +107,10 @@ class DifIntegrateViews(ctypes.Structure):
 
 
 WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 0, 1, 2, 3, 4, 8       # DIF_WELD_*
+COMP_COMPONENTS, COMP_STATUS, COMP_COUNT = 0, 1, 4                                                     # DIF_COMP_*
+SELECT_VERTICES, SELECT_TRIANGLES, SELECT_STATUS, SELECT_COUNT = 0, 1, 2, 4                            # DIF_SELECT_*
+EDGE_MAX_USE, EDGE_STATUS, EDGE_COUNT = 0, 1, 4                                                        # DIF_EDGE_*
+MESH_STATUS_BAD_INDEX, MESH_STATUS_RUNAWAY, MESH_STATUS_TABLE_FULL = 1, 2, 4                           # DIF_MESH_STATUS_*
 
 SIGNATURES = {
     "dif_version": (c_int32, []),
@@ -150,6 +154,13 @@ SIGNATURES = {
     "dif_mesh_weld_workspace_bytes": (c_int64, [c_int64]),
     "dif_mesh_weld": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DifWeldArgs), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_components_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dif_mesh_components": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_select_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dif_mesh_select": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_edge_census_workspace_bytes": (c_int64, [c_int64]),
+    "dif_mesh_edge_census": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_marching_cubes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_int32, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -149,6 +149,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_mesh.hip.h"
 #include "kernels_cloud.hip.h"
 #include "kernels_weld.hip.h"
+#include "kernels_components.hip.h"
 #include "kernels_optimize.hip.h"
 #include "kernels_track.hip.h"
 #include "kernels_photo.hip.h"
@@ -1711,6 +1712,170 @@ int dif_mesh_weld(const float* tri, const float* tri_std, const int64_t* tri_id,
     WeldTriangleFunctor ft{ws.corner_vertex, tri_id, vertices, triangles, triangle_id, ws.nsum, (float)args->resolution / args->voxel_size, (int)T, counts};
     if (launch_scan(ft, nullptr, (int)T, T, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
     hipLaunchKernelGGL(k_weld_normals, corners, block, 0, s, (const long long*)ws.nsum, (const int*)counts, normals);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- components, selection and edge census of an indexed mesh -------------------------------------------------------
+extern "C++" {
+// V vertices, K triangles that the kernels index with int (3 K as well)
+// `items` elements per thread, no grid-stride loop (the wave votes need every lane): n < 2^32, so the block count fits a launch
+static unsigned mesh_blocks(int64_t n, int items = 1) { return (unsigned)((n + (int64_t)DIF_BLOCK * items - 1) / ((int64_t)DIF_BLOCK * items)); }
+static bool mesh_sizes_ok(int64_t V, int64_t K) { return V >= 0 && K >= 0 && V < ((int64_t)1 << 31) && 3 * K < ((int64_t)1 << 31); }
+
+struct CompWs { int* parent; int* label; int* block_tmp; int64_t total_bytes; };
+
+static int carve_components(int64_t V, int64_t K, void* base, CompWs& ws) {
+    if (!mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    const size_t n = (size_t)(V > 0 ? V : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_parent = take(n * 4), o_label = take(n * 4), o_tmp = take(4096 * 4);
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.parent = (int*)(b + o_parent);
+        ws.label = (int*)(b + o_label);
+        ws.block_tmp = (int*)(b + o_tmp);
+    }
+    return DIF_OK;
+}
+
+struct SelectWs { int* mark; int* remap; int* block_tmp; size_t mark_bytes; int64_t total_bytes; };
+
+static int carve_select(int64_t V, int64_t K, void* base, SelectWs& ws) {
+    if (!mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    const size_t n = (size_t)(V > 0 ? V : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_mark = take(n * 4), o_remap = take(n * 4), o_tmp = take(4096 * 4);
+    ws.mark_bytes = n * 4;
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.mark = (int*)(b + o_mark);
+        ws.remap = (int*)(b + o_remap);
+        ws.block_tmp = (int*)(b + o_tmp);
+    }
+    return DIF_OK;
+}
+
+struct EdgeWs { EdgeTable t; size_t key_bytes, uses_bytes; int64_t cap; int64_t total_bytes; };
+
+static int carve_edges(int64_t K, void* base, EdgeWs& ws) {
+    if (K < 0 || 6 * K > ((int64_t)1 << 31)) return DIF_EINVAL;      // slots are indexed with 32 bits, and the probe loop's bound must fit them
+    int64_t cap = 64;
+    int bits = 6;
+    while (cap < 6 * K) { cap <<= 1; ++bits; }           // twice the triangle sides: never more than half full
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_key = take((size_t)cap * 8), o_uses = take((size_t)cap * 4);
+    ws.key_bytes = (size_t)cap * 8;
+    ws.uses_bytes = (size_t)cap * 4;
+    ws.cap = cap;
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.t.key = (unsigned long long*)(b + o_key);
+        ws.t.uses = (unsigned*)(b + o_uses);
+        ws.t.mask = (unsigned)(cap - 1);
+        ws.t.shift = 64 - bits;
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_components_workspace_bytes(int64_t V, int64_t K) {
+    CompWs ws;
+    if (carve_components(V, K, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_components(const int32_t* triangles, int64_t K, int64_t V, void* workspace, int64_t workspace_bytes, int32_t* vertex_component,
+                        int32_t* triangle_component, int32_t* comp_vertices, int32_t* comp_triangles, int32_t* counts, void* stream) {
+    if (!counts || !mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_COMP_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (V == 0 && K == 0) return DIF_OK;
+    if ((K > 0 && (!triangles || !triangle_component)) || (V > 0 && (!workspace || !vertex_component || !comp_vertices || !comp_triangles))) return DIF_EINVAL;
+    const dim3 block(DIF_BLOCK), per_vertex(mesh_blocks(V > 0 ? V : 1)), per_hook(mesh_blocks(K > 0 ? K : 1, HOOK_ITEMS));
+    if (V > 0) {
+        CompWs ws;
+        if (carve_components(V, K, workspace, ws) != DIF_OK) return DIF_EINVAL;
+        if (ws.total_bytes > workspace_bytes) return DIF_ENOSPACE;
+        hipLaunchKernelGGL(k_comp_init, per_vertex, block, 0, s, ws.parent, (int)V);
+        if (K > 0) hipLaunchKernelGGL(k_comp_hook, per_hook, block, 0, s, (const int*)triangles, (int)K, (int)V, ws.parent, counts);
+        hipLaunchKernelGGL(k_comp_flatten, per_vertex, block, 0, s, (const int*)ws.parent, (int)V, ws.label, counts);
+        DIF_CHECK_LAUNCH();
+        CompNumberFunctor f{ws.label, vertex_component, comp_vertices, comp_triangles, counts};
+        if (launch_scan(f, nullptr, (int)V, V, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+        hipLaunchKernelGGL(k_comp_vertices, dim3(mesh_blocks(V, CENSUS_ITEMS)), block, 0, s, (const int*)ws.label, (int)V, vertex_component, comp_vertices);
+    }
+    // (V = 0 with K > 0: every index is out of range — the same kernel reports it and writes the -1s, and dereferences nothing)
+    if (K > 0) {
+        if (V == 0) hipLaunchKernelGGL(k_comp_hook, per_hook, block, 0, s, (const int*)triangles, (int)K, 0, (int*)nullptr, counts);
+        hipLaunchKernelGGL(k_comp_triangles, dim3(mesh_blocks(K, CENSUS_ITEMS)), block, 0, s, (const int*)triangles, (int)K, (int)V, (const int*)vertex_component, triangle_component,
+                           comp_triangles);
+    }
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int64_t dif_mesh_select_workspace_bytes(int64_t V, int64_t K) {
+    SelectWs ws;
+    if (carve_select(V, K, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_select(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, const int64_t* triangle_id, int64_t V,
+                    int64_t K, const uint8_t* keep, void* workspace, int64_t workspace_bytes, float* out_vertices, float* out_normals, float* out_vertex_std,
+                    int32_t* out_triangles, int64_t* out_triangle_id, int32_t* counts, void* stream) {
+    if (!counts || !mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_SELECT_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (K == 0) return DIF_OK;                       // no triangle, so no kept vertex either
+    if (!triangles || !triangle_id || !keep || !workspace || !out_triangles || !out_triangle_id) return DIF_EINVAL;
+    if (V > 0 && (!vertices || !normals || !vertex_std || !out_vertices || !out_normals || !out_vertex_std)) return DIF_EINVAL;
+    SelectWs ws;
+    if (carve_select(V, K, workspace, ws) != DIF_OK) return DIF_EINVAL;
+    if (ws.total_bytes > workspace_bytes) return DIF_ENOSPACE;
+    if (hipMemsetAsync(ws.mark, 0, ws.mark_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_select_mark, dim3(mesh_blocks(K)), dim3(DIF_BLOCK), 0, s, (const int*)triangles, keep, (int)K, (int)V, ws.mark, counts);
+    DIF_CHECK_LAUNCH();
+    if (V > 0) {
+        SelectVertexFunctor fv{ws.mark, (const unsigned*)vertices, (const unsigned*)normals, (const unsigned*)vertex_std, (unsigned*)out_vertices,
+                               (unsigned*)out_normals, (unsigned*)out_vertex_std, ws.remap, counts};
+        if (launch_scan(fv, nullptr, (int)V, V, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+    }
+    SelectTriangleFunctor ft{(const int*)triangles, triangle_id, keep, ws.remap, out_triangles, out_triangle_id, (int)V, counts};
+    return launch_scan(ft, nullptr, (int)K, K, ws.block_tmp, s);
+}
+
+int64_t dif_mesh_edge_census_workspace_bytes(int64_t K) {
+    EdgeWs ws;
+    if (carve_edges(K, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const int32_t* vertex_component, int64_t C, void* workspace,
+                         int64_t workspace_bytes, int32_t* comp_edges, int32_t* comp_boundary, int32_t* counts, void* stream) {
+    if (!counts || !mesh_sizes_ok(V, K) || 6 * K > ((int64_t)1 << 31) || C < 0 || C > V) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_EDGE_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (C > 0) {
+        if (!comp_edges || !comp_boundary) return DIF_EINVAL;
+        if (hipMemsetAsync(comp_edges, 0, sizeof(int32_t) * (size_t)C, s) != hipSuccess) return DIF_ELAUNCH;
+        if (hipMemsetAsync(comp_boundary, 0, sizeof(int32_t) * (size_t)C, s) != hipSuccess) return DIF_ELAUNCH;
+    }
+    if (K == 0) return DIF_OK;
+    if (!triangles || !workspace || (V > 0 && !vertex_component)) return DIF_EINVAL;
+    EdgeWs ws;
+    if (carve_edges(K, workspace, ws) != DIF_OK) return DIF_EINVAL;
+    if (ws.total_bytes > workspace_bytes) return DIF_ENOSPACE;
+    if (hipMemsetAsync(ws.t.key, 0xFF, ws.key_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+    if (hipMemsetAsync(ws.t.uses, 0, ws.uses_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+    hipLaunchKernelGGL(k_edge_insert, dim3(mesh_blocks(3 * K)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)triangles, (int)(3 * K), (int)V, counts);
+    hipLaunchKernelGGL(k_edge_slots, dim3(mesh_blocks(ws.cap, CENSUS_SLOT_ITEMS)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)vertex_component, (int)C, comp_edges, comp_boundary, counts);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

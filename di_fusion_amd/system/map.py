@@ -631,11 +631,12 @@ class DenseIndexedMap:
         o = self._cache_out
         return o[0][:n], o[1][:n], o[2][:n]
 
-    def indexed_mesh(self, voxel_resolution: int = None):
+    def indexed_mesh(self, voxel_resolution: int = None, min_component_triangles: int = 0):
         """The mesh cache as an indexed mesh (`system.mesh.IndexedMesh`: shared vertices, area-weighted vertex normals, int32 triangles),
         welded on the GPU by the lattice edge a vertex sits on (DESIGN.md "Indexed mesh").  `voxel_resolution`: the resolution the cache was
         extracted at (default: that of the last extract); corners that are not on that lattice stay unwelded and are counted
-        (`counts["unkeyed"]`).  None while the cache is empty."""
+        (`counts["unkeyed"]`).  `min_component_triangles` > 0: without the connected components of fewer triangles (the fragments a fused
+        map carries beside its surfaces; `IndexedMesh.remove_small_components`).  None while the cache is empty."""
         from . import mesh as mesh_mod
         t = self.mesh_cache_tensors()
         if t is None:
@@ -643,7 +644,8 @@ class DenseIndexedMap:
         if voxel_resolution is None:
             voxel_resolution = self._xbuf[0][0]
         with torch.cuda.device(self.device):
-            return mesh_mod.weld(t[0], t[2], t[1], list(self._cmap.bound_min), float(self._cmap.voxel_size), int(voxel_resolution), self.n_xyz)
+            m = mesh_mod.weld(t[0], t[2], t[1], list(self._cmap.bound_min), float(self._cmap.voxel_size), int(voxel_resolution), self.n_xyz)
+            return m.remove_small_components(min_component_triangles) if min_component_triangles > 0 else m
 
     MIN_EXTRACT_ROWS = 1 << 15
     EXTRACT_ROWS_FLOOR = 1 << 12        # rows that `extract_buffer_bytes` never takes away

@@ -1,6 +1,8 @@
 """Indexed mesh: the triangle soup of the mesh cache welded by lattice edge, with area-weighted vertex normals (`dif_mesh_weld`), and a PLY
 writer.  No reference counterpart: the reference hands its soup to Open3D (`merge_close_vertices`, `compute_vertex_normals`, commented out in
-its main loop as too slow).  The key rule and why the weld is not by position: DESIGN.md "Indexed mesh".
+its main loop as too slow).  The key rule and why the weld is not by position: DESIGN.md "Indexed mesh".  On top of the weld: connected
+components, an edge census and the selection of a sub-mesh (`dif_mesh_components`, `dif_mesh_edge_census`, `dif_mesh_select`; DESIGN.md
+"Components of an indexed mesh").
 """
 from __future__ import annotations
 
@@ -18,7 +20,9 @@ COUNT_NAMES = ("vertices", "triangles", "dropped", "unkeyed", "status")
 class IndexedMesh:
     """vertices (V,3) f32, normals (V,3) f32 (unit, or zero for a vertex without a triangle), vertex_std (V,) f32, triangles (K,3) i32,
     triangle_flatten_id (K,) i64 — torch tensors on the device that welded them (`.cpu()` for a host copy) — and `counts`: vertices, triangles
-    kept, triangles dropped (a repeated index after welding), unkeyed soup corners (not on the lattice: each a vertex of its own), status."""
+    kept, triangles dropped (a repeated index after welding), unkeyed soup corners (not on the lattice: each a vertex of its own), status.
+    A mesh derived from another carries its own vertices, triangles and status (`select`) and `components_removed` on top
+    (`remove_small_components`)."""
 
     def __init__(self, vertices, normals, vertex_std, triangles, triangle_flatten_id, counts: dict):
         self.vertices = vertices
@@ -31,6 +35,39 @@ class IndexedMesh:
     def cpu(self) -> "IndexedMesh":
         return IndexedMesh(self.vertices.cpu(), self.normals.cpu(), self.vertex_std.cpu(), self.triangles.cpu(), self.triangle_flatten_id.cpu(),
                            self.counts)
+
+    def components(self) -> "MeshComponents":
+        """Connected components (`components`): per vertex, per triangle, and the size of each."""
+        return components(self.triangles, int(self.vertices.shape[0]))
+
+    def topology(self) -> "MeshTopology":
+        """`components()` plus, per component, its edges, its boundary edges (used by one triangle: 0 = closed) and V - E + F (2 = a sphere),
+        and the most triangles on any one edge (above 2 = not a manifold)."""
+        c = self.components()
+        n_edges, n_boundary, max_edge_use, status = edge_census(self.triangles, c.vertex_component, c.count)
+        return MeshTopology(c.vertex_component, c.triangle_component, c.n_vertices, c.n_triangles, c.count, c.status | status, n_edges, n_boundary,
+                            c.n_vertices - n_edges + c.n_triangles, max_edge_use)
+
+    def select(self, triangle_mask: torch.Tensor) -> "IndexedMesh":
+        """The sub-mesh of the triangles where `triangle_mask` (K,) is set: the vertices they use, renumbered in ascending order, the triangles in
+        their order.  Attributes are copied bit for bit; NORMALS ARE NOT RECOMPUTED — exact when whole components go (`remove_small_components`);
+        a vertex on the cut of any other mask keeps the normal summed over its former triangles."""
+        return _select(self, triangle_mask, None)
+
+    def remove_small_components(self, min_triangles: int = 0, keep_largest: Optional[int] = None) -> "IndexedMesh":
+        """Without the components of fewer than `min_triangles` triangles; `keep_largest=k`: of the rest, only the k with the most triangles (ties
+        go to the lower component id).  Vertices that no kept triangle uses go too.  The mask is built on the device; the only synchronisations
+        are the two read-backs of counts.  `counts["components_removed"]` of the result says how many went."""
+        c = self.components()
+        keep = c.n_triangles >= int(min_triangles)
+        if keep_largest is not None:
+            order = torch.sort(torch.where(keep, c.n_triangles, torch.full_like(c.n_triangles, -1)), descending=True, stable=True).indices
+            largest = torch.zeros_like(keep)
+            largest[order[:max(int(keep_largest), 0)]] = True
+            keep = keep & largest
+        tc = c.triangle_component.long()
+        mask = (tc >= 0) & keep[tc.clamp(min=0)] if c.count > 0 else torch.zeros_like(tc, dtype=torch.bool)
+        return _select(self, mask, c.count - (keep & (c.n_triangles > 0)).sum().to(torch.int32))
 
     def write_ply(self, path):
         """Binary little-endian PLY: x y z nx ny nz quality (= std) as float32 per vertex, faces as uchar count + three int indices."""
@@ -107,3 +144,139 @@ def weld(vertices: torch.Tensor, std: torch.Tensor, ids: torch.Tensor, bound_min
         raise RuntimeError(f"libdifusion: dif_mesh_weld reported status {c[_lib.WELD_STATUS]} (its class table overflowed)")
     V, K = c[_lib.WELD_VERTICES], c[_lib.WELD_KEPT]
     return IndexedMesh(out_v[:V], out_n[:V], out_s[:V], out_t[:K], out_i[:K], dict(zip(COUNT_NAMES, c[:len(COUNT_NAMES)])))
+
+
+# ---- components, selection, edge census (DESIGN.md "Components of an indexed mesh") -----------------------------------------------------
+class MeshComponents:
+    """vertex_component (V,) i32, triangle_component (K,) i32 (-1: the triangle holds an index outside [0, V)), n_vertices (C,) i32 and
+    n_triangles (C,) i32 — device tensors — `count` = C and `status` (0, or `_lib.MESH_STATUS_BAD_INDEX`).  Components are numbered in
+    ascending order of their lowest vertex id; a vertex without a triangle is a component of its own."""
+
+    def __init__(self, vertex_component, triangle_component, n_vertices, n_triangles, count: int, status: int = 0):
+        self.vertex_component = vertex_component
+        self.triangle_component = triangle_component
+        self.n_vertices = n_vertices
+        self.n_triangles = n_triangles
+        self.count = int(count)
+        self.status = int(status)
+
+
+class MeshTopology(MeshComponents):
+    """`MeshComponents` plus n_edges (C,), n_boundary (C,) (edges with one triangle), euler (C,) = V - E + F — device i32 — and `max_edge_use`."""
+
+    def __init__(self, vertex_component, triangle_component, n_vertices, n_triangles, count, status, n_edges, n_boundary, euler, max_edge_use: int):
+        super().__init__(vertex_component, triangle_component, n_vertices, n_triangles, count, status)
+        self.n_edges = n_edges
+        self.n_boundary = n_boundary
+        self.euler = euler
+        self.max_edge_use = int(max_edge_use)
+
+
+def _check_status(status: int, what: str):
+    if status & ~_lib.MESH_STATUS_BAD_INDEX:
+        raise RuntimeError(f"libdifusion: {what} reported status {status} (an iteration bound or its edge table was exceeded)")
+
+
+def _check_triangles(triangles: torch.Tensor, what: str) -> int:
+    _lib.require_cuda(triangles)
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise RuntimeError(f"{what}: triangles must be (K,3) int32; got {tuple(triangles.shape)} {triangles.dtype}")
+    return int(triangles.shape[0])
+
+
+def components(triangles: torch.Tensor, n_vertices: int) -> MeshComponents:
+    """The flat operator: triangles (K,3) i32 on the GPU over vertices 0..n_vertices-1 -> `MeshComponents`.  Reads the counts back (one
+    synchronisation) to slice the per-component sizes."""
+    K, V = _check_triangles(triangles, "components"), int(n_vertices)
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_components_workspace_bytes(V, K))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_components cannot index {V} vertices, {K} triangles (V and 3 K must stay below 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        vc = torch.empty((V,), dtype=torch.int32, device=dev)
+        tc = torch.empty((K,), dtype=torch.int32, device=dev)
+        nv = torch.empty((V,), dtype=torch.int32, device=dev)
+        nt = torch.empty((V,), dtype=torch.int32, device=dev)
+        counts = torch.empty((_lib.COMP_COUNT,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_components(_lib.ptr(triangles), K, V, _lib.ptr(ws), ws_bytes, _lib.ptr(vc), _lib.ptr(tc), _lib.ptr(nv), _lib.ptr(nt),
+                                           _lib.ptr(counts), _lib.stream_ptr()), "dif_mesh_components")
+        c = counts.cpu().tolist()
+    _check_status(c[_lib.COMP_STATUS], "dif_mesh_components")
+    C = c[_lib.COMP_COMPONENTS]
+    return MeshComponents(vc, tc, nv[:C], nt[:C], C, c[_lib.COMP_STATUS])
+
+
+def edge_census(triangles: torch.Tensor, vertex_component: torch.Tensor, n_components: int):
+    """The flat operator: triangles (K,3) i32 and the component of every vertex (V,) i32 with values below `n_components`, on the GPU ->
+    (n_edges (C,) i32, n_boundary (C,) i32, max_edge_use, status).  An edge is counted with the component of its lower end point; a triangle
+    side with equal end points is no edge.  One synchronisation (the counts)."""
+    K = _check_triangles(triangles, "edge_census")
+    _lib.require_cuda(vertex_component)
+    if vertex_component.dtype != torch.int32 or vertex_component.dim() != 1:
+        raise RuntimeError("edge_census: vertex_component must be (V,) int32")
+    V, C = int(vertex_component.shape[0]), int(n_components)
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_edge_census_workspace_bytes(K))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_edge_census cannot index {K} triangles (6 K must not pass 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ne = torch.empty((C,), dtype=torch.int32, device=dev)
+        nb = torch.empty((C,), dtype=torch.int32, device=dev)
+        counts = torch.empty((_lib.EDGE_COUNT,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_edge_census(_lib.ptr(triangles), K, V, _lib.ptr(vertex_component), C, _lib.ptr(ws), ws_bytes, _lib.ptr(ne), _lib.ptr(nb),
+                                            _lib.ptr(counts), _lib.stream_ptr()), "dif_mesh_edge_census")
+        c = counts.cpu().tolist()
+    _check_status(c[_lib.EDGE_STATUS], "dif_mesh_edge_census")
+    return ne, nb, c[_lib.EDGE_MAX_USE], c[_lib.EDGE_STATUS]
+
+
+def select(vertices: torch.Tensor, normals: torch.Tensor, vertex_std: torch.Tensor, triangles: torch.Tensor, triangle_flatten_id: torch.Tensor,
+           keep: torch.Tensor) -> IndexedMesh:
+    """The flat operator behind `IndexedMesh.select`: the arrays of an indexed mesh on the GPU and `keep` (K,) bool or uint8 -> `IndexedMesh`.
+    `counts`: vertices, triangles, status (`_lib.MESH_STATUS_BAD_INDEX`: a kept triangle held an index outside [0, V) and was dropped)."""
+    return _select(IndexedMesh(vertices, normals, vertex_std, triangles, triangle_flatten_id, {}), keep, None)
+
+
+def _select(m: IndexedMesh, keep: torch.Tensor, components_removed: Optional[torch.Tensor]) -> IndexedMesh:
+    """`components_removed`: a device int32 scalar that travels back with the counts (no synchronisation of its own)."""
+    K = _check_triangles(m.triangles, "select")
+    _lib.require_cuda(m.vertices, m.normals, m.vertex_std, m.triangle_flatten_id, keep)
+    V = int(m.vertices.shape[0])
+    if m.vertices.dtype != torch.float32 or m.normals.dtype != torch.float32 or m.vertex_std.dtype != torch.float32 or \
+            m.triangle_flatten_id.dtype != torch.int64:
+        raise RuntimeError("select: vertices, normals and vertex_std must be float32, triangle_flatten_id int64")
+    if tuple(m.vertices.shape) != (V, 3) or tuple(m.normals.shape) != (V, 3) or tuple(m.vertex_std.shape) != (V,) or \
+            tuple(m.triangle_flatten_id.shape) != (K,) or tuple(keep.shape) != (K,):
+        raise RuntimeError(f"select: expected (V,3), (V,3), (V,), (K,3), (K,), (K,); got {tuple(m.vertices.shape)}, {tuple(m.normals.shape)}, "
+                           f"{tuple(m.vertex_std.shape)}, {tuple(m.triangles.shape)}, {tuple(m.triangle_flatten_id.shape)}, {tuple(keep.shape)}")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"select: the mask must be bool or uint8; got {keep.dtype}")
+    dev = m.triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_select_workspace_bytes(V, K))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_select cannot index {V} vertices, {K} triangles (V and 3 K must stay below 2^31)")
+    with torch.cuda.device(dev):
+        keep8 = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        out_v = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        out_n = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        out_s = torch.empty((V,), dtype=torch.float32, device=dev)
+        out_t = torch.empty((K, 3), dtype=torch.int32, device=dev)
+        out_i = torch.empty((K,), dtype=torch.int64, device=dev)
+        counts = torch.empty((_lib.SELECT_COUNT + 1,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_select(_lib.ptr(m.vertices), _lib.ptr(m.normals), _lib.ptr(m.vertex_std), _lib.ptr(m.triangles),
+                                       _lib.ptr(m.triangle_flatten_id), V, K, _lib.ptr(keep8), _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), _lib.ptr(out_n),
+                                       _lib.ptr(out_s), _lib.ptr(out_t), _lib.ptr(out_i), _lib.ptr(counts), _lib.stream_ptr()), "dif_mesh_select")
+        counts[_lib.SELECT_COUNT:] = components_removed if components_removed is not None else 0
+        c = counts.cpu().tolist()
+    _check_status(c[_lib.SELECT_STATUS], "dif_mesh_select")
+    nv, nk = c[_lib.SELECT_VERTICES], c[_lib.SELECT_TRIANGLES]
+    out = dict(vertices=nv, triangles=nk, status=c[_lib.SELECT_STATUS])
+    if components_removed is not None:
+        out["components_removed"] = c[_lib.SELECT_COUNT]
+    return IndexedMesh(out_v[:nv], out_n[:nv], out_s[:nv], out_t[:nk], out_i[:nk], out)

@@ -428,6 +428,40 @@ int dif_mesh_weld(const float* tri, const float* tri_std, const int64_t* tri_id,
                   int64_t workspace_bytes, float* vertices, float* normals, float* vertex_std, int32_t* triangles, int64_t* triangle_id,
                   int32_t* counts, void* stream);
 
+/* ---- components, selection and edge census of an indexed mesh (no reference counterpart; DESIGN.md "Components of an indexed mesh") ------ */
+/* All integer, so every output is a pure function of the input.  Each entry point clears its own counts on every call; each workspace size is
+ * answered on the host (-1: a negative size, or an index would pass 2^31: V >= 2^31 or 3 K >= 2^31; the edge census: 6 K > 2^31).
+ * Status bits (all three): 1 = a triangle holds an index outside [0, V) (never dereferenced), 2 = an iteration bound was exceeded (cannot
+ * happen; reported instead of looping), 4 = the edge table overflowed (cannot happen: it holds twice the triangle sides). */
+enum { DIF_MESH_STATUS_BAD_INDEX = 1, DIF_MESH_STATUS_RUNAWAY = 2, DIF_MESH_STATUS_TABLE_FULL = 4 };
+
+/* Connected components: two vertices are connected if a triangle names both.  Every vertex belongs to one; a vertex without a triangle is a
+ * component of its own with 0 triangles.  Components are numbered 0..C-1 in ascending order of their LOWEST VERTEX ID.  A triangle with an
+ * index outside [0, V) joins nothing and gets triangle_component -1 (status bit 1).
+ * vertex_component (V), triangle_component (K), comp_vertices / comp_triangles (V: the first C are written) i32;
+ * counts (int32[DIF_COMP_COUNT], device). */
+enum { DIF_COMP_COMPONENTS = 0, DIF_COMP_STATUS = 1, DIF_COMP_COUNT = 4 };
+int64_t dif_mesh_components_workspace_bytes(int64_t V, int64_t K);
+int dif_mesh_components(const int32_t* triangles, int64_t K, int64_t V, void* workspace, int64_t workspace_bytes, int32_t* vertex_component,
+                        int32_t* triangle_component, int32_t* comp_vertices, int32_t* comp_triangles, int32_t* counts, void* stream);
+
+/* The sub-mesh of the triangles with keep[t] != 0: the vertices they name in ascending order of their old id, attributes copied bit for bit
+ * (normals are NOT recomputed), kept triangles in input order with remapped indices and their ids.  A kept triangle with an index outside
+ * [0, V) is dropped (status bit 1).  Outputs sized (V,3), (V,3), (V), (K,3), (K); rows beyond the counts are not written. */
+enum { DIF_SELECT_VERTICES = 0, DIF_SELECT_TRIANGLES = 1, DIF_SELECT_STATUS = 2, DIF_SELECT_COUNT = 4 };
+int64_t dif_mesh_select_workspace_bytes(int64_t V, int64_t K);
+int dif_mesh_select(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, const int64_t* triangle_id, int64_t V,
+                    int64_t K, const uint8_t* keep, void* workspace, int64_t workspace_bytes, float* out_vertices, float* out_normals, float* out_vertex_std,
+                    int32_t* out_triangles, int64_t* out_triangle_id, int32_t* counts, void* stream);
+
+/* Undirected edges (a triangle side with two different end points; the sides of a triangle with an index outside [0, V) are skipped, status
+ * bit 1) per component of their lower end point: comp_edges[c] = distinct edges, comp_boundary[c] = edges that exactly one triangle side names
+ * (both int32[C], cleared here); counts[DIF_EDGE_MAX_USE] = the most sides that name one edge.  vertex_component (V) with values in [0, C). */
+enum { DIF_EDGE_MAX_USE = 0, DIF_EDGE_STATUS = 1, DIF_EDGE_COUNT = 4 };
+int64_t dif_mesh_edge_census_workspace_bytes(int64_t K);
+int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const int32_t* vertex_component, int64_t C, void* workspace,
+                         int64_t workspace_bytes, int32_t* comp_edges, int32_t* comp_boundary, int32_t* counts, void* stream);
+
 /* Flat marching cubes = ext/marching_cubes mc.cpp:3-16.  indexer (nx,ny,nz) i64, valid_blocks (K) i64,
  * vec_batch_mapping (V) i32, cube_sdf/std (B,R,R,R) f32.  counters[DIF_C_T] receives the triangle count.      */
 int dif_marching_cubes(const int64_t* indexer, int32_t nx, int32_t ny, int32_t nz, const int64_t* valid_blocks,
