@@ -95,6 +95,12 @@ class DifWeldArgs(ctypes.Structure):
     _fields_ = [("bound_min", c_float * 3), ("voxel_size", c_float), ("resolution", c_int32), ("n_xyz", c_int32 * 3)]
 
 
+class DifRasterArgs(ctypes.Structure):
+    """include/difusion.h: dif_raster_args_t"""
+    _fields_ = [("world_to_cam", c_float * 12), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("z_near", c_float),
+                ("height", c_int32), ("width", c_int32), ("cull_backfaces", c_int32)]
+
+
 class DifOptimizeViews(ctypes.Structure):
     """include/difusion.h: dif_optimize_views_t"""
     _fields_ = [("row_slot", c_void_p), ("row_xyz", c_void_p), ("row_sdf", c_void_p), ("uniq_slot", c_void_p), ("slot_u", c_void_p), ("slot_flag", c_void_p),
@@ -111,6 +117,8 @@ COMP_COMPONENTS, COMP_STATUS, COMP_COUNT = 0, 1, 4                              
 SELECT_VERTICES, SELECT_TRIANGLES, SELECT_STATUS, SELECT_COUNT = 0, 1, 2, 4                            # DIF_SELECT_*
 EDGE_MAX_USE, EDGE_STATUS, EDGE_COUNT = 0, 1, 4                                                        # DIF_EDGE_*
 MESH_STATUS_BAD_INDEX, MESH_STATUS_RUNAWAY, MESH_STATUS_TABLE_FULL = 1, 2, 4                           # DIF_MESH_STATUS_*
+RASTER_PIXELS_HIT, RASTER_DRAWN, RASTER_CLIPPED, RASTER_DEGENERATE, RASTER_CULLED, RASTER_OFFSCREEN, RASTER_LARGE, RASTER_STATUS, RASTER_COUNT = range(9)   # DIF_RASTER_*
+RASTER_THREAD_PIXELS = 64                                                                              # DIF_RASTER_THREAD_PIXELS
 
 SIGNATURES = {
     "dif_version": (c_int32, []),
@@ -161,6 +169,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_mesh_edge_census_workspace_bytes": (c_int64, [c_int64]),
     "dif_mesh_edge_census": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
+    "dif_mesh_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_marching_cubes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_int32, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -150,6 +150,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_cloud.hip.h"
 #include "kernels_weld.hip.h"
 #include "kernels_components.hip.h"
+#include "kernels_raster.hip.h"
 #include "kernels_optimize.hip.h"
 #include "kernels_track.hip.h"
 #include "kernels_photo.hip.h"
@@ -1876,6 +1877,70 @@ int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const i
     if (hipMemsetAsync(ws.t.uses, 0, ws.uses_bytes, s) != hipSuccess) return DIF_ELAUNCH;
     hipLaunchKernelGGL(k_edge_insert, dim3(mesh_blocks(3 * K)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)triangles, (int)(3 * K), (int)V, counts);
     hipLaunchKernelGGL(k_edge_slots, dim3(mesh_blocks(ws.cap, CENSUS_SLOT_ITEMS)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)vertex_component, (int)C, comp_edges, comp_boundary, counts);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- rendering an indexed mesh ----------------------------------------------------------------------------------------
+extern "C++" {
+struct RasterWs { RasterVertex* pv; unsigned long long* zbuf; int* large_list; int64_t total_bytes; };
+
+static bool raster_sizes_ok(int64_t V, int64_t K, int64_t H, int64_t W) {
+    return mesh_sizes_ok(V, K) && H > 0 && W > 0 && H < ((int64_t)1 << 31) && W < ((int64_t)1 << 31) && H * W < ((int64_t)1 << 31);
+}
+
+static int carve_raster(int64_t V, int64_t K, int64_t H, int64_t W, void* base, RasterWs& ws) {
+    if (!raster_sizes_ok(V, K, H, W)) return DIF_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_pv = take((size_t)(V > 0 ? V : 1) * sizeof(RasterVertex)), o_z = take((size_t)(H * W) * 8), o_list = take((size_t)(K > 0 ? K : 1) * 4);
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.pv = (RasterVertex*)(b + o_pv);
+        ws.zbuf = (unsigned long long*)(b + o_z);
+        ws.large_list = (int*)(b + o_list);
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_render_workspace_bytes(int64_t V, int64_t K, int64_t H, int64_t W) {
+    RasterWs ws;
+    if (carve_raster(V, K, H, W, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_render(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, int64_t V, int64_t K,
+                    const dif_raster_args_t* args, void* workspace, int64_t workspace_bytes, float* depth, float* normal, float* std_out,
+                    int32_t* triangle, int32_t* counts, void* stream) {
+    if (!args || !counts) return DIF_EINVAL;
+    const int64_t H = args->height, W = args->width;
+    if (!raster_sizes_ok(V, K, H, W)) return DIF_EINVAL;
+    if (!(args->fx > 0.0f) || !(args->fy > 0.0f) || __builtin_isinf(args->fx) || __builtin_isinf(args->fy)) return DIF_EINVAL;
+    if (!(args->z_near >= 0.0f) || __builtin_isinf(args->z_near)) return DIF_EINVAL;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || !depth || !normal || !std_out || !triangle) return DIF_EINVAL;
+    if ((V > 0 && (!vertices || !normals || !vertex_std)) || (K > 0 && !triangles)) return DIF_EINVAL;
+    RasterWs ws;
+    if (carve_raster(V, K, H, W, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_RASTER_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    RasterCam cam;
+    for (int k = 0; k < 12; ++k) cam.r[k] = args->world_to_cam[k];
+    cam.fx = args->fx; cam.fy = args->fy; cam.cx = args->cx; cam.cy = args->cy; cam.z_near = args->z_near;
+    cam.H = (int)H; cam.W = (int)W; cam.cull = args->cull_backfaces != 0;
+    const int64_t npix = H * W;
+    const dim3 block(DIF_BLOCK);
+    hipLaunchKernelGGL(k_raster_project, dim3(mesh_blocks(V > npix ? V : npix)), block, 0, s, vertices, (int)V, cam, ws.pv, ws.zbuf, (int)npix);
+    if (K > 0) {
+        hipLaunchKernelGGL(k_raster_triangles, dim3(mesh_blocks(K)), block, 0, s, (const int*)triangles, (int)K, (int)V, (const RasterVertex*)ws.pv, cam.H, cam.W,
+                           cam.cull, ws.zbuf, ws.large_list, counts);
+        const int64_t large_blocks = K < RASTER_LARGE_BLOCKS ? K : RASTER_LARGE_BLOCKS;
+        hipLaunchKernelGGL(k_raster_large, dim3((unsigned)large_blocks), block, 0, s, (const int*)triangles, (int)K, (int)V, (const RasterVertex*)ws.pv, cam.H, cam.W,
+                           cam.cull, ws.zbuf, (const int*)ws.large_list, (const int*)counts);
+    }
+    hipLaunchKernelGGL(k_raster_resolve, dim3(mesh_blocks(npix)), block, 0, s, (const unsigned long long*)ws.zbuf, (const int*)triangles, (int)K, (int)V,
+                       (const RasterVertex*)ws.pv, normals, vertex_std, cam.H, cam.W, cam.cull, depth, normal, std_out, triangle, counts);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

@@ -647,6 +647,21 @@ class DenseIndexedMap:
             m = mesh_mod.weld(t[0], t[2], t[1], list(self._cmap.bound_min), float(self._cmap.voxel_size), int(voxel_resolution), self.n_xyz)
             return m.remove_small_components(min_component_triangles) if min_component_triangles > 0 else m
 
+    def render_view(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False, mesh=None,
+                    min_component_triangles: int = 0):
+        """Depth, normal, std and triangle-index images (`system.mesh.MeshRender`) of the map's mesh from the camera-to-world `pose` — a
+        `tracker.Pose`, a 4x4 matrix, anything `Pose.of` accepts; `intrinsics` = (fx, fy, cx, cy) or an object with those attributes.
+        Renders `mesh` (an `IndexedMesh`, e.g. one kept from an earlier `indexed_mesh()`), or `indexed_mesh(min_component_triangles=...)`
+        when it is None.  The depth image follows the convention of the input depth frames (NaN = nothing there), so it can be held against
+        one.  A triangle that reaches behind `z_near` vanishes as a whole; normals are in the map's frame (DESIGN.md "Rendering an indexed
+        mesh").  None while the cache is empty."""
+        if mesh is None:
+            mesh = self.indexed_mesh(min_component_triangles=min_component_triangles)
+            if mesh is None:
+                return None
+        with torch.cuda.device(self.device):
+            return mesh.render(pose, intrinsics, height, width, z_near=z_near, cull_backfaces=cull_backfaces)
+
     MIN_EXTRACT_ROWS = 1 << 15
     EXTRACT_ROWS_FLOOR = 1 << 12        # rows that `extract_buffer_bytes` never takes away
 

@@ -2,7 +2,8 @@
 writer.  No reference counterpart: the reference hands its soup to Open3D (`merge_close_vertices`, `compute_vertex_normals`, commented out in
 its main loop as too slow).  The key rule and why the weld is not by position: DESIGN.md "Indexed mesh".  On top of the weld: connected
 components, an edge census and the selection of a sub-mesh (`dif_mesh_components`, `dif_mesh_edge_census`, `dif_mesh_select`; DESIGN.md
-"Components of an indexed mesh").
+"Components of an indexed mesh").  And a look at it: depth, normal, std and triangle-index images from a camera pose (`dif_mesh_render`;
+DESIGN.md "Rendering an indexed mesh").
 """
 from __future__ import annotations
 
@@ -68,6 +69,10 @@ class IndexedMesh:
         tc = c.triangle_component.long()
         mask = (tc >= 0) & keep[tc.clamp(min=0)] if c.count > 0 else torch.zeros_like(tc, dtype=torch.bool)
         return _select(self, mask, c.count - (keep & (c.n_triangles > 0)).sum().to(torch.int32))
+
+    def render(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> "MeshRender":
+        """Depth, normal, std and triangle-index images of this mesh from the camera-to-world `pose` (`render`)."""
+        return render(self.vertices, self.normals, self.vertex_std, self.triangles, pose, intrinsics, height, width, z_near, cull_backfaces)
 
     def write_ply(self, path):
         """Binary little-endian PLY: x y z nx ny nz quality (= std) as float32 per vertex, faces as uchar count + three int indices."""
@@ -280,3 +285,86 @@ def _select(m: IndexedMesh, keep: torch.Tensor, components_removed: Optional[tor
     if components_removed is not None:
         out["components_removed"] = c[_lib.SELECT_COUNT]
     return IndexedMesh(out_v[:nv], out_n[:nv], out_s[:nv], out_t[:nk], out_i[:nk], out)
+
+
+# ---- rendering (DESIGN.md "Rendering an indexed mesh") ---------------------------------------------------------------------------------
+RENDER_COUNT_NAMES = ("pixels_hit", "drawn", "clipped", "degenerate", "culled", "offscreen", "large", "status")
+
+
+class MeshRender:
+    """depth (H,W) f32 (camera z; NaN where nothing was hit — the project's invalid depth: `ext.unproject_depth` turns it into NaN points),
+    normal (H,W,3) f32 (unit, in the mesh's frame, NOT turned towards the camera; zero where nothing was hit), std (H,W) f32 (NaN where nothing
+    was hit), triangle (H,W) i32 (index into the mesh's triangles, -1 where nothing was hit) — device tensors, `.cpu()` for a host copy — and
+    `counts`: pixels hit, triangles drawn, clipped (a vertex at or behind `z_near`, non-finite, or far outside the image: THE WHOLE TRIANGLE
+    GOES, there is no near-plane clipping), degenerate, culled, offscreen, large (the drawn ones a workgroup walked), status."""
+
+    def __init__(self, depth, normal, std, triangle, counts: dict):
+        self.depth = depth
+        self.normal = normal
+        self.std = std
+        self.triangle = triangle
+        self.counts = dict(counts)
+
+    def cpu(self) -> "MeshRender":
+        return MeshRender(self.depth.cpu(), self.normal.cpu(), self.std.cpu(), self.triangle.cpu(), self.counts)
+
+
+def world_to_cam_rows(pose) -> np.ndarray:
+    """camera-to-world pose (a `tracker.Pose`, a 4x4 array or tensor, anything `Pose.of` accepts) -> the 12 float32 of the row-major 3x4
+    world-to-camera transform: R^T and -R^T t in float64, rounded once (like `tracker._rows34`)."""
+    from .tracker import Pose
+    if isinstance(pose, torch.Tensor):
+        pose = pose.detach().cpu().numpy()
+    if isinstance(pose, np.ndarray):
+        if pose.shape != (4, 4):
+            raise RuntimeError(f"render: a pose matrix must be 4x4; got {pose.shape}")
+        pose = pose.astype(np.float64)
+    p = Pose.of(pose)
+    return np.concatenate([p.R.T, -(p.R.T @ p.t)[:, None]], axis=1).astype(np.float32).reshape(12)
+
+
+def raster_args(pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> _lib.DifRasterArgs:
+    a = _lib.DifRasterArgs()
+    for k, x in enumerate(world_to_cam_rows(pose)):
+        a.world_to_cam[k] = float(x)
+    if all(hasattr(intrinsics, n) for n in ("fx", "fy", "cx", "cy")):
+        intrinsics = (intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy)
+    a.fx, a.fy, a.cx, a.cy = (float(x) for x in intrinsics)
+    a.z_near = float(z_near)
+    a.height, a.width, a.cull_backfaces = int(height), int(width), int(bool(cull_backfaces))
+    return a
+
+
+def render(vertices: torch.Tensor, normals: torch.Tensor, vertex_std: torch.Tensor, triangles: torch.Tensor, pose, intrinsics, height: int,
+           width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> MeshRender:
+    """The flat operator: the arrays of an indexed mesh on the GPU, the camera-to-world `pose`, `intrinsics` = (fx, fy, cx, cy) or an object
+    with those attributes -> `MeshRender` of `height` x `width` pixels.  Pixel (u, v) is column and row with its centre at integer
+    coordinates, x = (u - cx) / fx * z (the convention of `ext.unproject_depth`).  One synchronisation (the counts)."""
+    K = _check_triangles(triangles, "render")
+    _lib.require_cuda(vertices, normals, vertex_std)
+    V = int(vertices.shape[0])
+    if vertices.dtype != torch.float32 or normals.dtype != torch.float32 or vertex_std.dtype != torch.float32:
+        raise RuntimeError("render: vertices, normals and vertex_std must be float32")
+    if tuple(vertices.shape) != (V, 3) or tuple(normals.shape) != (V, 3) or tuple(vertex_std.shape) != (V,):
+        raise RuntimeError(f"render: expected (V,3), (V,3), (V,); got {tuple(vertices.shape)}, {tuple(normals.shape)}, {tuple(vertex_std.shape)}")
+    args = raster_args(pose, intrinsics, height, width, z_near, cull_backfaces)
+    H, W = int(args.height), int(args.width)
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_render_workspace_bytes(V, K, H, W))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_render failed: {_lib.ERRORS[-1]}: cannot index {V} vertices, {K} triangles, {H} x {W} pixels "
+                           "(the image must not be empty; V, 3 K and H W must stay below 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+        normal = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        std = torch.empty((H, W), dtype=torch.float32, device=dev)
+        triangle = torch.empty((H, W), dtype=torch.int32, device=dev)
+        counts = torch.empty((_lib.RASTER_COUNT,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_render(_lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(vertex_std), _lib.ptr(triangles), V, K, ctypes.byref(args),
+                                       _lib.ptr(ws), ws_bytes, _lib.ptr(depth), _lib.ptr(normal), _lib.ptr(std), _lib.ptr(triangle), _lib.ptr(counts),
+                                       _lib.stream_ptr()), "dif_mesh_render")
+        c = counts.cpu().tolist()
+    _check_status(c[_lib.RASTER_STATUS], "dif_mesh_render")
+    return MeshRender(depth, normal, std, triangle, dict(zip(RENDER_COUNT_NAMES, c)))

@@ -462,6 +462,37 @@ int64_t dif_mesh_edge_census_workspace_bytes(int64_t K);
 int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const int32_t* vertex_component, int64_t C, void* workspace,
                          int64_t workspace_bytes, int32_t* comp_edges, int32_t* comp_boundary, int32_t* counts, void* stream);
 
+/* Depth, normal, std and triangle-index images of an indexed mesh seen from a pinhole camera (DESIGN.md "Rendering an indexed mesh").
+ * Pixel (u, v) is column and row, its centre sits at integer coordinates, x = (u - cx) / fx * z (dif_unproject's convention).
+ * Camera point = world_to_cam (row-major 3x4, float32) applied as ((r0 x + r1 y) + r2 z) + t.  A vertex is valid when that point is finite,
+ * its z > z_near and its screen position, snapped to 1/256 pixel, stays below 2^22 in magnitude.  Coverage is decided in integers on the
+ * snapped positions (top-left rule: a pixel centre on a shared edge belongs to exactly one triangle); the nearest perspective-correct depth
+ * wins a pixel, equal depths go to the lowest triangle index — every output is independent of the schedule.
+ * THERE IS NO NEAR-PLANE CLIPPING: a triangle with an invalid vertex vanishes as a whole (counted as clipped).
+ * depth (H,W) f32: NaN where nothing was hit;  normal (H,W,3) f32: barycentric blend of the vertex normals, renormalised, in the MESH's frame,
+ * not turned towards the camera, zero where nothing was hit (or the blend has no direction);  std (H,W) f32: NaN where nothing was hit;
+ * triangle (H,W) i32: -1 where nothing was hit.
+ * counts (int32[DIF_RASTER_COUNT], device): pixels hit; triangles DRAWN (they reached the pixel walk; LARGE = those of them whose pixel box
+ * holds more than DIF_RASTER_THREAD_PIXELS pixels, walked by a workgroup instead of a thread); CLIPPED (an invalid vertex); DEGENERATE (zero
+ * area after snapping); CULLED (cull_backfaces, and cross(p1 - p0, p2 - p0) points away from the camera); OFFSCREEN (no pixel centre inside
+ * the bounding box, clipped to the image); status = 0 or DIF_MESH_STATUS_BAD_INDEX (a triangle holds an index outside [0, V): dropped, never
+ * dereferenced).  Every triangle is in exactly one of drawn / clipped / degenerate / culled / offscreen / bad index.
+ * DIF_EINVAL: H or W <= 0, H W or 3 K >= 2^31, V >= 2^31, fx or fy not positive and finite, z_near negative or not finite, a NULL output or
+ * counts pointer (or a NULL mesh array that V or K says is not empty), a workspace that is NULL, not aligned to 16 bytes, or smaller than
+ * dif_mesh_render_workspace_bytes (which answers -1 for sizes it cannot index).  K = 0 or V = 0 is valid: an empty image. */
+typedef struct {
+    float world_to_cam[12];
+    float fx, fy, cx, cy, z_near;
+    int32_t height, width, cull_backfaces;
+} dif_raster_args_t;
+enum { DIF_RASTER_PIXELS_HIT = 0, DIF_RASTER_DRAWN = 1, DIF_RASTER_CLIPPED = 2, DIF_RASTER_DEGENERATE = 3, DIF_RASTER_CULLED = 4,
+       DIF_RASTER_OFFSCREEN = 5, DIF_RASTER_LARGE = 6, DIF_RASTER_STATUS = 7, DIF_RASTER_COUNT = 8 };
+enum { DIF_RASTER_THREAD_PIXELS = 64 };
+int64_t dif_mesh_render_workspace_bytes(int64_t V, int64_t K, int64_t H, int64_t W);
+int dif_mesh_render(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, int64_t V, int64_t K,
+                    const dif_raster_args_t* args, void* workspace, int64_t workspace_bytes, float* depth, float* normal, float* std,
+                    int32_t* triangle, int32_t* counts, void* stream);
+
 /* Flat marching cubes = ext/marching_cubes mc.cpp:3-16.  indexer (nx,ny,nz) i64, valid_blocks (K) i64,
  * vec_batch_mapping (V) i32, cube_sdf/std (B,R,R,R) f32.  counters[DIF_C_T] receives the triangle count.      */
 int dif_marching_cubes(const int64_t* indexer, int32_t nx, int32_t ny, int32_t nz, const int64_t* valid_blocks,
