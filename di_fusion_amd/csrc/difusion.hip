@@ -264,9 +264,9 @@ int dif_point_box_filter(const float* points, const float* normals, int64_t N, f
     if (nwords >= ((int64_t)1 << 31)) return DIF_EINVAL;
     if (launch_scan(f, (const int*)(status + 1), 0, nwords, scratch, s) != DIF_OK) return DIF_ELAUNCH;      // device-side length: the cloud's own box grid
     hipLaunchKernelGGL(k_pbf_accumulate, dim3(grid_for(N)), dim3(DIF_BLOCK), 0, s, points, normals, N, voxel_size, (const unsigned*)mm,
-                       (const uint32_t*)bits, (const int*)word_rank, (long long*)sums, (const int*)status);
+                       (const uint32_t*)bits, (const int*)word_rank, (long long*)sums, (const int*)status, max_cells);
     hipLaunchKernelGGL(k_pbf_finish, dim3(grid_for(N)), dim3(DIF_BLOCK), 0, s, (const long long*)sums, (const int*)out_count, out_points, out_normals,
-                       bits, points, N, voxel_size, (const unsigned*)mm, (const int*)status);
+                       bits, points, N, voxel_size, (const unsigned*)mm, (const int*)status, max_cells);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(FE_TILE * FE_TILE) k_normal_weight(const float
 
 // point_box_filter (system/tracker.py:13-23): mean point / mean normal per voxel_size box, boxes in ascending linear id
 // (x fastest).  Bounds -> box bitmap -> ordered ranks -> order-independent fixed-point sums -> means.
-struct BoxGrid { float minb[3]; int n[3]; };
+#include "pbf_grid.hip.h"      // BoxGrid, pbf_grid, pbf_cell: plain host/device code, walked on the CPU by tools/pbf_grid_check.cpp
 
 __device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
@@ -265,28 +265,23 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_bounds(const float* __restric
     }
 }
 
-__device__ __forceinline__ BoxGrid pbf_grid(const unsigned* __restrict__ mm, float vs) {
-    BoxGrid G;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float mn = ord2f(mm[a]) - vs * 0.5f, mx = ord2f(mm[3 + a]) + vs * 0.5f;     // tracker.py:15-16
-        G.minb[a] = mn;
-        G.n[a] = (int)floorf((mx - mn) / vs) + 16;                                    // tracker.py:18
-    }
-    return G;
-}
-
-__device__ __forceinline__ int64_t pbf_cell(const BoxGrid& G, const float* p, float vs) {
-    int64_t cx = (int64_t)floorf((p[0] - G.minb[0]) / vs), cy = (int64_t)floorf((p[1] - G.minb[1]) / vs), cz = (int64_t)floorf((p[2] - G.minb[2]) / vs);
-    return cx + cy * G.n[0] + cz * (int64_t)G.n[0] * G.n[1];                          // tracker.py:17,19
+// The grid of the bounds k_pbf_bounds left in `mm`, and pbf_grid's verdict on it.  Every kernel below runs this on the same six words and
+// the same arguments, so all of them see the same grid and the same verdict.
+__device__ __forceinline__ int pbf_grid_of(const unsigned* __restrict__ mm, float vs, int64_t max_cells, BoxGrid& G) {
+    const float lo[3] = {ord2f(mm[0]), ord2f(mm[1]), ord2f(mm[2])}, hi[3] = {ord2f(mm[3]), ord2f(mm[4]), ord2f(mm[5])};
+    return pbf_grid(lo, hi, vs, max_cells, G);
 }
 
 __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_mark(const float* __restrict__ pts, int64_t N, float vs, const unsigned* __restrict__ mm,
                                                       uint32_t* __restrict__ bits, int64_t max_cells, int* __restrict__ status) {
-    const BoxGrid G = pbf_grid(mm, vs);
-    const int64_t cells = (int64_t)G.n[0] * G.n[1] * G.n[2];
-    if (blockIdx.x == 0 && threadIdx.x == 0) status[1] = cells > max_cells ? 0 : (int)((cells + 31) >> 5);      // bitmap words in use: all the rank scan walks
-    if (cells > max_cells) { if (blockIdx.x == 0 && threadIdx.x == 0) status[0] = 1; return; }
+    BoxGrid G;
+    const int verdict = pbf_grid_of(mm, vs, max_cells, G);
+    if (verdict != PBF_GRID_OK) {        // a cloud the grid cannot hold (NaN / Inf coordinate, a far outlier, more than max_cells): refused before any bitmap write
+        if (blockIdx.x == 0 && threadIdx.x == 0) { status[0] = verdict; status[1] = 0; }
+        return;
+    }
+    const int64_t cells = (int64_t)G.n[0] * G.n[1] * G.n[2];      // <= max_cells: no overflow
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[1] = (int)((cells + 31) >> 5);      // bitmap words in use: all the rank scan walks
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t c = pbf_cell(G, pts + i * 3, vs);
         uint32_t b = 1u << (c & 31);
@@ -306,9 +301,10 @@ struct BoxRankFunctor {      // exclusive prefix of popcounts per bitmap word = 
 __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_accumulate(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t N, float vs,
                                                             const unsigned* __restrict__ mm, const uint32_t* __restrict__ bits,
                                                             const int* __restrict__ word_rank, long long* __restrict__ sums /* [boxes][8] */,
-                                                            const int* __restrict__ status) {
+                                                            const int* __restrict__ status, int64_t max_cells) {
     if (status[0]) return;
-    const BoxGrid G = pbf_grid(mm, vs);
+    BoxGrid G;
+    pbf_grid_of(mm, vs, max_cells, G);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t c = pbf_cell(G, pts + i * 3, vs);
         int r = word_rank[c >> 5] + __popc(bits[c >> 5] & ((1u << (c & 31)) - 1u));
@@ -324,7 +320,8 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_accumulate(const float* __res
 
 __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_finish(const long long* __restrict__ sums, const int* __restrict__ n_boxes, float* __restrict__ out_pts,
                                                         float* __restrict__ out_nrm, uint32_t* __restrict__ bits, const float* __restrict__ pts, int64_t N,
-                                                        float vs, const unsigned* __restrict__ mm, const int* __restrict__ status) {
+                                                        float vs, const unsigned* __restrict__ mm, const int* __restrict__ status, int64_t max_cells) {
+    if (status[0]) return;                                   // a refused cloud: no box was marked, no sum taken, the bitmap is still all-zero
     const int nb = n_boxes[0];
     NO_PACKED_F32
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < (int64_t)nb * 3; e += (int64_t)gridDim.x * blockDim.x) {
@@ -333,8 +330,8 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_pbf_finish(const long long* __res
         out_pts[e] = (float)((double)sums[r * 8 + a] * (1.0 / 16777216.0)) / cnt;
         out_nrm[e] = (float)((double)sums[r * 8 + 3 + a] * (1.0 / 16777216.0)) / cnt;
     }
-    if (status[0]) return;
-    const BoxGrid G = pbf_grid(mm, vs);                      // restore the bitmap to all-zero for the next call
+    BoxGrid G;                                               // restore the bitmap to all-zero for the next call
+    pbf_grid_of(mm, vs, max_cells, G);
     NO_PACKED_F32
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t c = pbf_cell(G, pts + i * 3, vs);

@@ -119,7 +119,9 @@ _PBF_SCRATCH = {}
 def point_box_filter(points: torch.Tensor, normals: torch.Tensor, voxel_size: float, max_cells: int = 1 << 27):
     """Voxel-mean down-sampling, reference `system/tracker.py:13-23` (the step right before `integrate_keyframe`):
     (N,3) points + normals -> (n_boxes,3) means, boxes ordered by ascending linear box id.  `max_cells` bounds the box grid
-    (bounding box of the cloud / voxel_size + 16 per axis); 2^27 cells = 16 MB of bitmap."""
+    (bounding box of the cloud / voxel_size + 16 per axis); 2^27 cells = 16 MB of bitmap.
+    Input contract: every coordinate finite and the grid within `max_cells`.  A cloud that breaks it is refused with RuntimeError before
+    anything is written (csrc/pbf_grid.hip.h), and the next call works as usual.  NaN normals are not checked."""
     _lib.require_cuda(points, normals)
     N = points.size(0)
     dev = points.device
@@ -138,6 +140,8 @@ def point_box_filter(points: torch.Tensor, normals: torch.Tensor, voxel_size: fl
                                                     _lib.ptr(cnt), _lib.ptr(bits), int(max_cells), _lib.ptr(word_rank), _lib.ptr(sums),
                                                     _lib.ptr(scratch), _lib.stream_ptr()), "dif_point_box_filter")
         st = scratch[4102].item()
+    if st == 2:
+        raise RuntimeError("point_box_filter: the cloud has a NaN or infinite coordinate (strip such rows first, as tracker.track_camera does)")
     if st != 0:
         raise RuntimeError("point_box_filter: the cloud's box grid exceeds max_cells")
     n = int(cnt.item())

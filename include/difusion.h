@@ -230,7 +230,12 @@ int dif_depth_frontend(const float* depth, int32_t H, int32_t W, float fx, float
 /* system/tracker.py:13-23 point_box_filter: mean point and mean normal per voxel_size box; boxes come out in ascending
  * linear box id (x fastest), out_count[0] (device) = number of boxes.  out_points/out_normals: (N,3) capacity.
  * bits: uint32[(max_cells+31)/32] all-zero on entry and on exit; word_rank: int32[(max_cells+31)/32]; sums: int64[N*8];
- * scratch: int32[4200].  If the box grid of the cloud exceeds max_cells, scratch[4102] is set and nothing is produced. */
+ * scratch: int32[4200].
+ * Input contract: every coordinate of `points` is finite and the box grid (per axis floor((max - min + voxel_size) / voxel_size) + 16
+ * boxes) has every axis count below 2^31 - 16 and at most max_cells boxes in all.  A cloud that breaks it is refused on the device,
+ * before the bitmap or any output is written: scratch[4102] = 1 (grid beyond max_cells: also a far outlier) or 2 (a NaN or infinite
+ * coordinate), out_count[0] = 0, `bits` still all-zero, so the next call needs no repair.  The return value stays DIF_OK: the verdict is
+ * only known on the device (csrc/pbf_grid.hip.h states the rule).  Normals are not checked. */
 int dif_point_box_filter(const float* points, const float* normals, int64_t N, float voxel_size, float* out_points,
                          float* out_normals, int32_t* out_count, uint32_t* bits, int64_t max_cells, int32_t* word_rank,
                          int64_t* sums, int32_t* scratch, void* stream);
