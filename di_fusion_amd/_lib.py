@@ -101,6 +101,11 @@ class DifRasterArgs(ctypes.Structure):
                 ("height", c_int32), ("width", c_int32), ("cull_backfaces", c_int32)]
 
 
+class DifColourArgs(ctypes.Structure):
+    """include/difusion.h: dif_colour_args_t"""
+    _fields_ = [("depth_tol", c_float), ("min_cos2", c_float), ("edge_gate", c_int32), ("reserved", c_int32)]
+
+
 class DifOptimizeViews(ctypes.Structure):
     """include/difusion.h: dif_optimize_views_t"""
     _fields_ = [("row_slot", c_void_p), ("row_xyz", c_void_p), ("row_sdf", c_void_p), ("uniq_slot", c_void_p), ("slot_u", c_void_p), ("slot_flag", c_void_p),
@@ -119,6 +124,8 @@ EDGE_MAX_USE, EDGE_STATUS, EDGE_COUNT = 0, 1, 4                                 
 MESH_STATUS_BAD_INDEX, MESH_STATUS_RUNAWAY, MESH_STATUS_TABLE_FULL = 1, 2, 4                           # DIF_MESH_STATUS_*
 RASTER_PIXELS_HIT, RASTER_DRAWN, RASTER_CLIPPED, RASTER_DEGENERATE, RASTER_CULLED, RASTER_OFFSCREEN, RASTER_LARGE, RASTER_STATUS, RASTER_COUNT = range(9)   # DIF_RASTER_*
 RASTER_THREAD_PIXELS = 64                                                                              # DIF_RASTER_THREAD_PIXELS
+COLOUR_USED, COLOUR_NO_HIT, COLOUR_BAD_COLOUR, COLOUR_DEPTH, COLOUR_EDGE, COLOUR_GRAZING, COLOUR_STATUS, COLOUR_COUNT = 0, 1, 2, 3, 4, 5, 6, 8   # DIF_COLOUR_*
+COLOUR_WEIGHT_ONE = 65536                                                                              # fixed point of the colour weights
 
 SIGNATURES = {
     "dif_version": (c_int32, []),
@@ -172,6 +179,10 @@ SIGNATURES = {
     "dif_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     "dif_mesh_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_colour_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
+    "dif_mesh_colour_view": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), POINTER(DifColourArgs), c_void_p, c_void_p,
+                                       c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_colour_resolve": (c_int32, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_marching_cubes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_int32, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -151,6 +151,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_weld.hip.h"
 #include "kernels_components.hip.h"
 #include "kernels_raster.hip.h"
+#include "kernels_colour.hip.h"
 #include "kernels_optimize.hip.h"
 #include "kernels_track.hip.h"
 #include "kernels_photo.hip.h"
@@ -1911,25 +1912,29 @@ int64_t dif_mesh_render_workspace_bytes(int64_t V, int64_t K, int64_t H, int64_t
     return ws.total_bytes;
 }
 
-int dif_mesh_render(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, int64_t V, int64_t K,
-                    const dif_raster_args_t* args, void* workspace, int64_t workspace_bytes, float* depth, float* normal, float* std_out,
-                    int32_t* triangle, int32_t* counts, void* stream) {
-    if (!args || !counts) return DIF_EINVAL;
-    const int64_t H = args->height, W = args->width;
-    if (!raster_sizes_ok(V, K, H, W)) return DIF_EINVAL;
-    if (!(args->fx > 0.0f) || !(args->fy > 0.0f) || __builtin_isinf(args->fx) || __builtin_isinf(args->fy)) return DIF_EINVAL;
-    if (!(args->z_near >= 0.0f) || __builtin_isinf(args->z_near)) return DIF_EINVAL;
-    if (!workspace || ((uintptr_t)workspace & 15) != 0 || !depth || !normal || !std_out || !triangle) return DIF_EINVAL;
-    if ((V > 0 && (!vertices || !normals || !vertex_std)) || (K > 0 && !triangles)) return DIF_EINVAL;
-    RasterWs ws;
-    if (carve_raster(V, K, H, W, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_RASTER_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+// What dif_mesh_render and dif_mesh_colour_view refuse alike: the sizes, the camera, the workspace.
+static bool raster_call_ok(const dif_raster_args_t* args, int64_t V, int64_t K, const void* workspace) {
+    if (!args || !raster_sizes_ok(V, K, args->height, args->width)) return false;
+    if (!(args->fx > 0.0f) || !(args->fy > 0.0f) || __builtin_isinf(args->fx) || __builtin_isinf(args->fy)) return false;
+    if (!(args->z_near >= 0.0f) || __builtin_isinf(args->z_near)) return false;
+    return workspace && ((uintptr_t)workspace & 15) == 0;
+}
+
+extern "C++" {
+static RasterCam raster_cam(const dif_raster_args_t* args) {
     RasterCam cam;
     for (int k = 0; k < 12; ++k) cam.r[k] = args->world_to_cam[k];
     cam.fx = args->fx; cam.fy = args->fy; cam.cx = args->cx; cam.cy = args->cy; cam.z_near = args->z_near;
-    cam.H = (int)H; cam.W = (int)W; cam.cull = args->cull_backfaces != 0;
-    const int64_t npix = H * W;
+    cam.H = args->height; cam.W = args->width; cam.cull = args->cull_backfaces != 0;
+    return cam;
+}
+
+// The visibility passes of both: clears `counts` (int32[DIF_RASTER_COUNT]), then projection + z-buffer reset, the per-triangle walk, the
+// large-triangle walk.  Behind them ws.zbuf holds the winner of every pixel and counts everything but the pixels hit.
+static int raster_visibility(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, const RasterCam& cam, const RasterWs& ws,
+                             int32_t* counts, hipStream_t s) {
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_RASTER_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    const int64_t npix = (int64_t)cam.H * cam.W;
     const dim3 block(DIF_BLOCK);
     hipLaunchKernelGGL(k_raster_project, dim3(mesh_blocks(V > npix ? V : npix)), block, 0, s, vertices, (int)V, cam, ws.pv, ws.zbuf, (int)npix);
     if (K > 0) {
@@ -1939,8 +1944,70 @@ int dif_mesh_render(const float* vertices, const float* normals, const float* ve
         hipLaunchKernelGGL(k_raster_large, dim3((unsigned)large_blocks), block, 0, s, (const int*)triangles, (int)K, (int)V, (const RasterVertex*)ws.pv, cam.H, cam.W,
                            cam.cull, ws.zbuf, (const int*)ws.large_list, (const int*)counts);
     }
-    hipLaunchKernelGGL(k_raster_resolve, dim3(mesh_blocks(npix)), block, 0, s, (const unsigned long long*)ws.zbuf, (const int*)triangles, (int)K, (int)V,
-                       (const RasterVertex*)ws.pv, normals, vertex_std, cam.H, cam.W, cam.cull, depth, normal, std_out, triangle, counts);
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int dif_mesh_render(const float* vertices, const float* normals, const float* vertex_std, const int32_t* triangles, int64_t V, int64_t K,
+                    const dif_raster_args_t* args, void* workspace, int64_t workspace_bytes, float* depth, float* normal, float* std_out,
+                    int32_t* triangle, int32_t* counts, void* stream) {
+    if (!counts || !raster_call_ok(args, V, K, workspace)) return DIF_EINVAL;
+    if (!depth || !normal || !std_out || !triangle) return DIF_EINVAL;
+    if ((V > 0 && (!vertices || !normals || !vertex_std)) || (K > 0 && !triangles)) return DIF_EINVAL;
+    RasterWs ws;
+    if (carve_raster(V, K, args->height, args->width, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const RasterCam cam = raster_cam(args);
+    const int rc = raster_visibility(vertices, triangles, V, K, cam, ws, counts, s);
+    if (rc != DIF_OK) return rc;
+    hipLaunchKernelGGL(k_raster_resolve, dim3(mesh_blocks((int64_t)cam.H * cam.W)), dim3(DIF_BLOCK), 0, s, (const unsigned long long*)ws.zbuf, (const int*)triangles,
+                       (int)K, (int)V, (const RasterVertex*)ws.pv, normals, vertex_std, cam.H, cam.W, cam.cull, depth, normal, std_out, triangle, counts);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- colouring an indexed mesh ----------------------------------------------------------------------------------------
+// The workspace is the rasteriser's, then the int32[DIF_RASTER_COUNT] its visibility passes count into.
+static int64_t colour_counts_offset(int64_t V, int64_t K, int64_t H, int64_t W) {
+    RasterWs ws;
+    return carve_raster(V, K, H, W, nullptr, ws) == DIF_OK ? ws.total_bytes : -1;
+}
+
+int64_t dif_mesh_colour_workspace_bytes(int64_t V, int64_t K, int64_t H, int64_t W) {
+    const int64_t off = colour_counts_offset(V, K, H, W);
+    return off < 0 ? -1 : off + (int64_t)align256(sizeof(int32_t) * DIF_RASTER_COUNT);
+}
+
+int dif_mesh_colour_view(const float* vertices, const float* normals, const int32_t* triangles, int64_t V, int64_t K, const dif_raster_args_t* view,
+                         const dif_colour_args_t* gates, const float* rgb, const float* depth_in, void* workspace, int64_t workspace_bytes,
+                         uint64_t* accum, int32_t* counts, void* stream) {
+    if (!counts || !gates || !rgb || (V > 0 && !accum) || !raster_call_ok(view, V, K, workspace)) return DIF_EINVAL;
+    if (!(gates->depth_tol >= 0.0f) || __builtin_isinf(gates->depth_tol) || !(gates->min_cos2 >= 0.0f) || __builtin_isinf(gates->min_cos2)) return DIF_EINVAL;
+    if ((V > 0 && (!vertices || !normals)) || (K > 0 && !triangles)) return DIF_EINVAL;
+    RasterWs ws;
+    const int64_t off = colour_counts_offset(V, K, view->height, view->width);
+    if (off < 0 || dif_mesh_colour_workspace_bytes(V, K, view->height, view->width) > workspace_bytes) return DIF_EINVAL;
+    carve_raster(V, K, view->height, view->width, workspace, ws);
+    int32_t* raster_counts = (int32_t*)((char*)workspace + off);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_COLOUR_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    const RasterCam cam = raster_cam(view);
+    const int rc = raster_visibility(vertices, triangles, V, K, cam, ws, raster_counts, s);
+    if (rc != DIF_OK) return rc;
+    const ColourGates g{gates->depth_tol, gates->min_cos2, gates->edge_gate != 0};
+    hipLaunchKernelGGL(k_colour_splat, dim3(mesh_blocks((int64_t)cam.H * cam.W)), dim3(DIF_BLOCK), 0, s, (const unsigned long long*)ws.zbuf, (const int*)triangles,
+                       (int)K, (int)V, (const RasterVertex*)ws.pv, normals, rgb, depth_in, cam, g, (const int*)raster_counts, (unsigned long long*)accum, counts);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int dif_mesh_colour_resolve(const uint64_t* accum, int64_t V, uint64_t min_weight, uint8_t* rgb8, float* weight, int32_t* counts, void* stream) {
+    if (!counts || V < 0 || V >= ((int64_t)1 << 31) || (V > 0 && (!accum || !rgb8 || !weight))) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t), s) != hipSuccess) return DIF_ELAUNCH;
+    if (V == 0) return DIF_OK;
+    hipLaunchKernelGGL(k_colour_resolve, dim3(mesh_blocks(V)), dim3(DIF_BLOCK), 0, s, (const unsigned long long*)accum, (int)V, (unsigned long long)min_weight, rgb8,
+                       weight, counts);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

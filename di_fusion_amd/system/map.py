@@ -662,6 +662,22 @@ class DenseIndexedMap:
         with torch.cuda.device(self.device):
             return mesh.render(pose, intrinsics, height, width, z_near=z_near, cull_backfaces=cull_backfaces)
 
+    def coloured_mesh(self, views, voxel_resolution: int = None, min_component_triangles: int = 0, min_weight: float = 0.0, **gates):
+        """`indexed_mesh(voxel_resolution, min_component_triangles)` with vertex colours from RGB keyframes: `views` is an iterable of
+        (rgb (H,W,3) f32 in [0,1] — what `track_camera` takes —, depth (H,W) f32 or None, camera-to-world pose, intrinsics), tensors on the
+        map's device; `gates` are the keywords of `system.mesh.colour_args` (depth_tol, min_cos, edge_gate).  Every view is splatted onto the
+        vertices through the rasteriser, then the sums are resolved: `colors` (V,3) uint8, `color_weight` (V,), `counts["coloured"]`; a vertex
+        that no view saw with at least `min_weight` stays grey (DESIGN.md "Colouring an indexed mesh").  The map keeps no keyframes: they are
+        the caller's to keep (`tracker.all_pd_pose` has the poses).  None while the cache is empty."""
+        mesh = self.indexed_mesh(voxel_resolution, min_component_triangles)
+        if mesh is None:
+            return None
+        with torch.cuda.device(self.device):
+            col = mesh.colourer()
+            for rgb, depth, pose, intrinsics in views:
+                col.add_view(rgb, pose, intrinsics, depth=depth, **gates)
+            return col.resolve(min_weight)
+
     MIN_EXTRACT_ROWS = 1 << 15
     EXTRACT_ROWS_FLOOR = 1 << 12        # rows that `extract_buffer_bytes` never takes away
 

@@ -3,7 +3,8 @@ writer.  No reference counterpart: the reference hands its soup to Open3D (`merg
 its main loop as too slow).  The key rule and why the weld is not by position: DESIGN.md "Indexed mesh".  On top of the weld: connected
 components, an edge census and the selection of a sub-mesh (`dif_mesh_components`, `dif_mesh_edge_census`, `dif_mesh_select`; DESIGN.md
 "Components of an indexed mesh").  And a look at it: depth, normal, std and triangle-index images from a camera pose (`dif_mesh_render`;
-DESIGN.md "Rendering an indexed mesh").
+DESIGN.md "Rendering an indexed mesh").  And its colour: RGB keyframes splatted onto the vertices through that rasteriser (`dif_mesh_colour_view`,
+`dif_mesh_colour_resolve`; DESIGN.md "Colouring an indexed mesh").
 """
 from __future__ import annotations
 
@@ -23,19 +24,23 @@ class IndexedMesh:
     triangle_flatten_id (K,) i64 — torch tensors on the device that welded them (`.cpu()` for a host copy) — and `counts`: vertices, triangles
     kept, triangles dropped (a repeated index after welding), unkeyed soup corners (not on the lattice: each a vertex of its own), status.
     A mesh derived from another carries its own vertices, triangles and status (`select`) and `components_removed` on top
-    (`remove_small_components`)."""
+    (`remove_small_components`).  A coloured one (`colourer().resolve()`) carries `colors` (V,3) uint8 and `color_weight` (V,) f32 as well, and
+    `counts["coloured"]`; both are None otherwise."""
 
-    def __init__(self, vertices, normals, vertex_std, triangles, triangle_flatten_id, counts: dict):
+    def __init__(self, vertices, normals, vertex_std, triangles, triangle_flatten_id, counts: dict, colors=None, color_weight=None):
         self.vertices = vertices
         self.normals = normals
         self.vertex_std = vertex_std
         self.triangles = triangles
         self.triangle_flatten_id = triangle_flatten_id
         self.counts = dict(counts)
+        self.colors = colors
+        self.color_weight = color_weight
 
     def cpu(self) -> "IndexedMesh":
         return IndexedMesh(self.vertices.cpu(), self.normals.cpu(), self.vertex_std.cpu(), self.triangles.cpu(), self.triangle_flatten_id.cpu(),
-                           self.counts)
+                           self.counts, None if self.colors is None else self.colors.cpu(),
+                           None if self.color_weight is None else self.color_weight.cpu())
 
     def components(self) -> "MeshComponents":
         """Connected components (`components`): per vertex, per triangle, and the size of each."""
@@ -52,13 +57,15 @@ class IndexedMesh:
     def select(self, triangle_mask: torch.Tensor) -> "IndexedMesh":
         """The sub-mesh of the triangles where `triangle_mask` (K,) is set: the vertices they use, renumbered in ascending order, the triangles in
         their order.  Attributes are copied bit for bit; NORMALS ARE NOT RECOMPUTED — exact when whole components go (`remove_small_components`);
-        a vertex on the cut of any other mask keeps the normal summed over its former triangles."""
+        a vertex on the cut of any other mask keeps the normal summed over its former triangles.  COLOURS ARE DROPPED (the result has
+        `colors = None`): cull first, colour after."""
         return _select(self, triangle_mask, None)
 
     def remove_small_components(self, min_triangles: int = 0, keep_largest: Optional[int] = None) -> "IndexedMesh":
         """Without the components of fewer than `min_triangles` triangles; `keep_largest=k`: of the rest, only the k with the most triangles (ties
         go to the lower component id).  Vertices that no kept triangle uses go too.  The mask is built on the device; the only synchronisations
-        are the two read-backs of counts.  `counts["components_removed"]` of the result says how many went."""
+        are the two read-backs of counts.  `counts["components_removed"]` of the result says how many went.  Colours are dropped, as by
+        `select`: cull first, colour after."""
         c = self.components()
         keep = c.n_triangles >= int(min_triangles)
         if keep_largest is not None:
@@ -74,21 +81,32 @@ class IndexedMesh:
         """Depth, normal, std and triangle-index images of this mesh from the camera-to-world `pose` (`render`)."""
         return render(self.vertices, self.normals, self.vertex_std, self.triangles, pose, intrinsics, height, width, z_near, cull_backfaces)
 
+    def colourer(self) -> "MeshColourer":
+        """A `MeshColourer` over this mesh: add RGB keyframes with `.add_view`, then `.resolve()` for the coloured mesh."""
+        return MeshColourer(self)
+
     def write_ply(self, path):
-        """Binary little-endian PLY: x y z nx ny nz quality (= std) as float32 per vertex, faces as uchar count + three int indices."""
+        """Binary little-endian PLY: x y z nx ny nz quality (= std) as float32 per vertex — then red green blue as uchar if the mesh carries
+        colours; without them the file is what it always was — faces as uchar count + three int indices."""
         v = self.vertices.cpu().numpy()
-        vert = np.empty((v.shape[0],), dtype=[(n, "<f4") for n in ("x", "y", "z", "nx", "ny", "nz", "quality")])
+        floats = ("x", "y", "z", "nx", "ny", "nz", "quality")
+        rgb = ("red", "green", "blue") if self.colors is not None else ()
+        vert = np.empty((v.shape[0],), dtype=[(n, "<f4") for n in floats] + [(n, "u1") for n in rgb])
         n = self.normals.cpu().numpy()
         for k, name in enumerate(("x", "y", "z")):
             vert[name] = v[:, k]
             vert["n" + name] = n[:, k]
         vert["quality"] = self.vertex_std.cpu().numpy()
+        if rgb:
+            c = self.colors.cpu().numpy()
+            for k, name in enumerate(rgb):
+                vert[name] = c[:, k]
         t = self.triangles.cpu().numpy()
         face = np.empty((t.shape[0],), dtype=[("n", "u1"), ("v", "<i4", (3,))])
         face["n"] = 3
         face["v"] = t
         header = ("ply\nformat binary_little_endian 1.0\ncomment di_fusion_amd indexed mesh\n"
-                  f"element vertex {vert.shape[0]}\n" + "".join(f"property float {name}\n" for name in vert.dtype.names) +
+                  f"element vertex {vert.shape[0]}\n" + "".join(f"property float {name}\n" for name in floats) + "".join(f"property uchar {name}\n" for name in rgb) +
                   f"element face {face.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
         with open(path, "wb") as f:
             f.write(header.encode("ascii"))
@@ -96,12 +114,14 @@ class IndexedMesh:
             f.write(face.tobytes())
 
     def to_open3d(self):
-        """`open3d.geometry.TriangleMesh` with vertex normals (raises ImportError without Open3D)."""
+        """`open3d.geometry.TriangleMesh` with vertex normals, and vertex colours if the mesh carries them (raises ImportError without Open3D)."""
         import open3d as o3d
         m = o3d.geometry.TriangleMesh()
         m.vertices = o3d.utility.Vector3dVector(self.vertices.cpu().numpy().astype(np.float64))
         m.triangles = o3d.utility.Vector3iVector(self.triangles.cpu().numpy())
         m.vertex_normals = o3d.utility.Vector3dVector(self.normals.cpu().numpy().astype(np.float64))
+        if self.colors is not None:
+            m.vertex_colors = o3d.utility.Vector3dVector(self.colors.cpu().numpy().astype(np.float64) / 255.0)
         return m
 
 
@@ -368,3 +388,126 @@ def render(vertices: torch.Tensor, normals: torch.Tensor, vertex_std: torch.Tens
         c = counts.cpu().tolist()
     _check_status(c[_lib.RASTER_STATUS], "dif_mesh_render")
     return MeshRender(depth, normal, std, triangle, dict(zip(RENDER_COUNT_NAMES, c)))
+
+
+# ---- colouring (DESIGN.md "Colouring an indexed mesh") ---------------------------------------------------------------------------------
+COLOUR_COUNT_NAMES = ("used", "no_hit", "bad_colour", "depth", "edge", "grazing", "status")
+
+
+def colour_args(depth_tol: float = 0.02, min_cos: float = 0.3, edge_gate: bool = True) -> _lib.DifColourArgs:
+    """The gates of `colour_view`: `depth_tol` (metres; the depth gate against the view's depth frame, and the step that makes a pixel a
+    silhouette pixel for the edge gate), `min_cos` (the least |cos| between the blended normal and the view ray; squared here in float64 and
+    rounded to float32: the kernel compares cos^2), `edge_gate`."""
+    a = _lib.DifColourArgs()
+    a.depth_tol = float(depth_tol)
+    a.min_cos2 = float(np.float32(np.float64(min_cos) * np.float64(min_cos)))
+    a.edge_gate, a.reserved = int(bool(edge_gate)), 0
+    return a
+
+
+def colour_accumulator(n_vertices: int, device) -> torch.Tensor:
+    """A zeroed (V,4) uint64 accumulator for `colour_view` on `device` (allocated as int64 and viewed: the same bits)."""
+    return torch.zeros((int(n_vertices), 4), dtype=torch.int64, device=device).view(torch.uint64)
+
+
+def _check_mesh_arrays(vertices, normals, triangles, what: str):
+    K = _check_triangles(triangles, what)
+    _lib.require_cuda(vertices, normals)
+    V = int(vertices.shape[0])
+    if vertices.dtype != torch.float32 or normals.dtype != torch.float32:
+        raise RuntimeError(f"{what}: vertices and normals must be float32")
+    if tuple(vertices.shape) != (V, 3) or tuple(normals.shape) != (V, 3):
+        raise RuntimeError(f"{what}: expected (V,3), (V,3); got {tuple(vertices.shape)}, {tuple(normals.shape)}")
+    return V, K
+
+
+def colour_view(vertices: torch.Tensor, normals: torch.Tensor, triangles: torch.Tensor, accum: torch.Tensor, rgb: torch.Tensor, pose, intrinsics,
+                depth: Optional[torch.Tensor] = None, z_near: float = 0.05, cull_backfaces: bool = False, gates: Optional[_lib.DifColourArgs] = None,
+                workspace: Optional[torch.Tensor] = None) -> dict:
+    """The flat operator: ADDS the view `rgb` (H,W,3) f32 in [0,1] — with its depth frame `depth` (H,W) f32, or None — seen from the
+    camera-to-world `pose` to `accum` (V,4) uint64 (zeroed by the caller before the first view), all on the GPU.  Height and width are those
+    of `rgb`; pose, intrinsics, `z_near` and `cull_backfaces` as for `render`; `gates` from `colour_args` (default: its defaults).  Returns
+    the view's counts: pixels used, no_hit, bad_colour, depth, edge, grazing (each pixel in exactly one), status.  One synchronisation."""
+    V, K = _check_mesh_arrays(vertices, normals, triangles, "colour_view")
+    _lib.require_cuda(accum, rgb, depth)
+    if rgb.dtype != torch.float32 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise RuntimeError(f"colour_view: rgb must be (H,W,3) float32; got {tuple(rgb.shape)} {rgb.dtype}")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if depth is not None and (depth.dtype != torch.float32 or tuple(depth.shape) != (H, W)):
+        raise RuntimeError(f"colour_view: depth must be ({H},{W}) float32 like rgb; got {tuple(depth.shape)} {depth.dtype}")
+    if accum.dtype != torch.uint64 or tuple(accum.shape) != (V, 4):
+        raise RuntimeError(f"colour_view: accum must be ({V},4) uint64; got {tuple(accum.shape)} {accum.dtype}")
+    view = raster_args(pose, intrinsics, H, W, z_near, cull_backfaces)
+    gates = colour_args() if gates is None else gates
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_colour_workspace_bytes(V, K, H, W))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_colour_view failed: {_lib.ERRORS[-1]}: cannot index {V} vertices, {K} triangles, {H} x {W} pixels "
+                           "(the image must not be empty; V, 3 K and H W must stay below 2^31)")
+    with torch.cuda.device(dev):
+        if workspace is None or workspace.numel() < ws_bytes:
+            workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((_lib.COLOUR_COUNT,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_colour_view(_lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(triangles), V, K, ctypes.byref(view), ctypes.byref(gates),
+                                            _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(workspace), int(workspace.numel()), _lib.ptr(accum), _lib.ptr(counts),
+                                            _lib.stream_ptr()), "dif_mesh_colour_view")
+        c = counts.cpu().tolist()
+    _check_status(c[_lib.COLOUR_STATUS], "dif_mesh_colour_view")
+    return dict(zip(COLOUR_COUNT_NAMES, c))
+
+
+def colour_resolve(accum: torch.Tensor, min_weight: float = 0.0):
+    """The flat operator: `accum` (V,4) uint64 on the GPU -> (colors (V,3) uint8, color_weight (V,) f32, vertices coloured).  A vertex whose
+    summed weight (in pixels: one pixel seen head-on at the vertex weighs 1) is below `min_weight`, or zero, is grey (128, 128, 128) and
+    not counted.  One synchronisation (the count)."""
+    _lib.require_cuda(accum)
+    if accum.dtype != torch.uint64 or accum.dim() != 2 or accum.shape[1] != 4:
+        raise RuntimeError(f"colour_resolve: accum must be (V,4) uint64; got {tuple(accum.shape)} {accum.dtype}")
+    if not (min_weight >= 0.0) or min_weight >= 2.0 ** 47:
+        raise RuntimeError(f"colour_resolve: min_weight must lie in [0, 2^47); got {min_weight}")
+    V = int(accum.shape[0])
+    dev = accum.device
+    lib = _lib.load()
+    least = int(np.ceil(np.float64(min_weight) * _lib.COLOUR_WEIGHT_ONE))          # S >= ceil(x) <=> S >= x for the integer S
+    with torch.cuda.device(dev):
+        colors = torch.empty((V, 3), dtype=torch.uint8, device=dev)
+        weight = torch.empty((V,), dtype=torch.float32, device=dev)
+        counts = torch.empty((1,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_colour_resolve(_lib.ptr(accum), V, least, _lib.ptr(colors), _lib.ptr(weight), _lib.ptr(counts), _lib.stream_ptr()),
+                   "dif_mesh_colour_resolve")
+        n = int(counts.cpu()[0])
+    return colors, weight, n
+
+
+class MeshColourer:
+    """The colour accumulator of one `IndexedMesh`: `accum` (V,4) uint64 on the mesh's device (sum w r, sum w g, sum w b, sum w per vertex),
+    zeroed here; `views` = how many views went in.  The sums are integers, so the order of the views does not matter."""
+
+    def __init__(self, mesh: IndexedMesh):
+        _check_mesh_arrays(mesh.vertices, mesh.normals, mesh.triangles, "colourer")
+        self.mesh = mesh
+        self.views = 0
+        with torch.cuda.device(mesh.triangles.device):
+            self.accum = colour_accumulator(int(mesh.vertices.shape[0]), mesh.triangles.device)
+        self._ws = None
+
+    def add_view(self, rgb: torch.Tensor, pose, intrinsics, depth: Optional[torch.Tensor] = None, z_near: float = 0.05, cull_backfaces: bool = False,
+                 **gates) -> dict:
+        """Adds one keyframe (`colour_view`; `gates`: the keywords of `colour_args`) and returns its counts."""
+        m = self.mesh
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        need = int(_lib.load().dif_mesh_colour_workspace_bytes(int(m.vertices.shape[0]), int(m.triangles.shape[0]), H, W))
+        if need > 0 and (self._ws is None or self._ws.numel() < need):
+            with torch.cuda.device(m.triangles.device):
+                self._ws = torch.empty((need,), dtype=torch.uint8, device=m.triangles.device)
+        c = colour_view(m.vertices, m.normals, m.triangles, self.accum, rgb, pose, intrinsics, depth, z_near, cull_backfaces, colour_args(**gates), self._ws)
+        self.views += 1
+        return c
+
+    def resolve(self, min_weight: float = 0.0) -> IndexedMesh:
+        """A new `IndexedMesh` that shares this mesh's geometry tensors and carries `colors`, `color_weight` and `counts["coloured"]`; vertices
+        that no view saw (or saw with less than `min_weight`) are grey.  More views may be added afterwards, and resolved again."""
+        m = self.mesh
+        colors, weight, n = colour_resolve(self.accum, min_weight)
+        return IndexedMesh(m.vertices, m.normals, m.vertex_std, m.triangles, m.triangle_flatten_id, dict(m.counts, coloured=n), colors, weight)

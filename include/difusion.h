@@ -498,6 +498,42 @@ int dif_mesh_render(const float* vertices, const float* normals, const float* ve
                     const dif_raster_args_t* args, void* workspace, int64_t workspace_bytes, float* depth, float* normal, float* std,
                     int32_t* triangle, int32_t* counts, void* stream);
 
+/* Vertex colours of an indexed mesh from RGB keyframes (DESIGN.md "Colouring an indexed mesh").
+ * dif_mesh_colour_view ADDS one view to `accum` (uint64 (V,4), device: sum w r, sum w g, sum w b, sum w per vertex; the caller zeroes it once,
+ * before the first view) and clears and fills `counts` (int32[DIF_COLOUR_COUNT], device).  Visibility is dif_mesh_render's own: the same
+ * projection, walks and z-buffer for the same `view`, so the triangle that owns a pixel here is the one its triangle image names.
+ * rgb (H,W,3) f32 in [0,1] (clamped), depth_in (H,W) f32 or NULL: the depth frame that belongs to `rgb`.
+ * Every pixel falls into exactly one class, tested in this order:
+ *   NO_HIT      no triangle won the pixel;
+ *   BAD_COLOUR  one of the three rgb values is not finite;
+ *   DEPTH       depth_in given, and depth_in[p] is not finite or fabsf(depth_in[p] - d) > depth_tol (d = the float32 z-buffer depth);
+ *   EDGE        edge_gate != 0, and one of the 4-neighbours INSIDE the image is empty or has a z-buffer depth dn with fabsf(dn - d) > depth_tol
+ *               (a silhouette pixel would paint background colour onto the foreground under a one-pixel pose error);
+ *   GRAZING     with b0, b1, b2 the perspective-correct barycentrics of dif_mesh_render, n = (b0 n0 + b1 n1) + b2 n2 per component (not
+ *               normalised) and the view ray dw = R^T (rx, ry, 1), rx = ((double) i - cx) / fx, ry = ((double) j - cy) / fy, each component
+ *               (a rx + b ry) + c over column k of the rotation of world_to_cam, all in double: nd = (n.x dw.x + n.y dw.y) + n.z dw.z, nn and dd
+ *               likewise, cos2 = (nd nd) / (nn dd); grazing when !(nn > 0), cos2 is not finite, or cos2 < (double) min_cos2.  cos2 carries no
+ *               sign: the normals of a weld are not turned towards the camera;
+ *   USED        q_c = (uint64) rint(fmin(fmax((double) rgb_c, 0), 1) 255), w_k = (uint64) rint((b_k cos2) 65536) for the three vertices of
+ *               the oriented triangle; w_k q_r, w_k q_g, w_k q_b and w_k are added to accum[v_k] (a vertex with w_k == 0 receives nothing).
+ * One contribution is at most 2^16 * 255 < 2^24 (b_k <= 1, cos2 <= 1 up to rounding), so a 64-bit sum holds 2^40 of them: more than a million
+ * full-HD views onto ONE vertex.  The sums are integers: the order of pixels, views and waves does not show in them.
+ * counts[DIF_COLOUR_STATUS] = 0 or DIF_MESH_STATUS_BAD_INDEX (dropped, never dereferenced), as dif_mesh_render reports it.
+ * DIF_EINVAL: everything dif_mesh_render refuses (vertex_std and its images aside), a NULL rgb, gates or counts, a NULL accum with V > 0, depth_tol or min_cos2
+ * negative or not finite, a workspace smaller than dif_mesh_colour_workspace_bytes (-1 for sizes it cannot index; never less than
+ * dif_mesh_render_workspace_bytes: one workspace serves both).  K = 0 or V = 0 is valid: every pixel is NO_HIT.
+ * dif_mesh_colour_resolve: S = accum[v][3]; if S >= max(min_weight, 1): rgb8[v][c] = (2 accum[v][c] + S) / (2 S), the integer division rounded
+ * to nearest; else 128, 128, 128.  weight[v] = (float) ((double) S / 65536) either way.  counts (int32[1], device): the vertices coloured.
+ * DIF_EINVAL: V < 0 or >= 2^31, a NULL counts, a NULL array with V > 0.  V = 0 is valid. */
+typedef struct { float depth_tol, min_cos2; int32_t edge_gate, reserved; } dif_colour_args_t;
+enum { DIF_COLOUR_USED = 0, DIF_COLOUR_NO_HIT = 1, DIF_COLOUR_BAD_COLOUR = 2, DIF_COLOUR_DEPTH = 3, DIF_COLOUR_EDGE = 4,
+       DIF_COLOUR_GRAZING = 5, DIF_COLOUR_STATUS = 6, DIF_COLOUR_COUNT = 8 };
+int64_t dif_mesh_colour_workspace_bytes(int64_t V, int64_t K, int64_t H, int64_t W);
+int dif_mesh_colour_view(const float* vertices, const float* normals, const int32_t* triangles, int64_t V, int64_t K,
+                         const dif_raster_args_t* view, const dif_colour_args_t* gates, const float* rgb, const float* depth_in,
+                         void* workspace, int64_t workspace_bytes, uint64_t* accum, int32_t* counts, void* stream);
+int dif_mesh_colour_resolve(const uint64_t* accum, int64_t V, uint64_t min_weight, uint8_t* rgb8, float* weight, int32_t* counts, void* stream);
+
 /* Flat marching cubes = ext/marching_cubes mc.cpp:3-16.  indexer (nx,ny,nz) i64, valid_blocks (K) i64,
  * vec_batch_mapping (V) i32, cube_sdf/std (B,R,R,R) f32.  counters[DIF_C_T] receives the triangle count.      */
 int dif_marching_cubes(const int64_t* indexer, int32_t nx, int32_t ny, int32_t nz, const int64_t* valid_blocks,

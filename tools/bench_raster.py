@@ -42,8 +42,9 @@ def timed(call, warmup, reps):
     return dict(median=round(statistics.median(ms), 4), min=round(min(ms), 4), max=round(max(ms), 4))
 
 
-def per_launch(call, reps):
-    """mean device microseconds per kernel of one call, by kernel name; None if the profiler cannot start or records no kernel of the library"""
+def per_launch(call, reps, kernels=r"k_raster_\w+"):
+    """mean device microseconds per kernel of one call, by kernel name (those that match `kernels`, and the memsets); None if the profiler
+    cannot start or records no kernel of the library"""
     from torch.profiler import ProfilerActivity, profile
     try:
         prof = profile(activities=[ProfilerActivity.CUDA])
@@ -59,12 +60,12 @@ def per_launch(call, reps):
         prof.__exit__(None, None, None)
     out = {}
     for e in prof.key_averages():
-        m = re.search(r"k_raster_\w+", e.key)
+        m = re.search(kernels, e.key)
         name = m.group(0) if m else ("memset" if re.search(r"memset|fill", e.key, flags=re.I) else None)
         total = e.device_time_total if hasattr(e, "device_time_total") else e.cuda_time_total
         if name and total:
             out[name] = round(out.get(name, 0.0) + total / reps, 2)
-    return out if any(k.startswith("k_raster") for k in out) else None
+    return out if any(k != "memset" for k in out) else None
 
 
 class Renderer:
@@ -121,7 +122,8 @@ def weld_ms(soup, warmup, reps):
                                     "dif_mesh_weld"), warmup, reps)
 
 
-def c3_rows(model, frames, warmup, reps):
+def c3_scene(model, frames):
+    """the C3 bench stream after `frames` frames -> (stream, intrinsics, the soup of its mesh cache as `weld_ms` takes it, the welded mesh)"""
     from di_fusion_amd.stream import FusionStream
     scene, cfg = syn.config_c3()
     intr = syn.Intrinsic()
@@ -132,15 +134,23 @@ def c3_rows(model, frames, warmup, reps):
     m = st.map
     tri, tid, tstd = (t.clone() for t in m.mesh_cache_tensors())
     soup = (tri, tstd, tid, list(m._cmap.bound_min), float(m._cmap.voxel_size), st.resolution, m.n_xyz)
+    return st, intr, soup, M.weld(*soup)
+
+
+def c3_pose(i):
+    Rm, t = syn.orbit_pose(i, 0.3, 0.5)
+    pose = np.eye(4)
+    pose[:3, :3], pose[:3, 3] = Rm, t
+    return pose
+
+
+def c3_rows(model, frames, warmup, reps):
+    st, intr, soup, mesh = c3_scene(model, frames)
     w = weld_ms(soup, warmup, reps)
-    mesh = M.weld(*soup)
     rows = []
     for i in sorted({0, frames // 2, frames - 1}):
-        Rm, t = syn.orbit_pose(i, 0.3, 0.5)
-        pose = np.eye(4)
-        pose[:3, :3], pose[:3, 3] = Rm, t
-        row = measure(f"C3 bench stream after {frames} frames, pose of frame {i}", mesh, pose, intr, warmup, reps, input_depth=st.depth[i].reshape(intr.height, intr.width))
-        row.update(weld_ms_median=w["median"], soup_triangles=int(tri.shape[0]))
+        row = measure(f"C3 bench stream after {frames} frames, pose of frame {i}", mesh, c3_pose(i), intr, warmup, reps, input_depth=st.depth[i].reshape(intr.height, intr.width))
+        row.update(weld_ms_median=w["median"], soup_triangles=int(soup[0].shape[0]))
         rows.append(row)
     return rows
 
