@@ -326,7 +326,7 @@ static int cloud_build(const float* pc, int64_t n, int stride, float radius, int
     int rc = carve_cloud(n, wsp, ws);
     if (rc != DIF_OK) return rc;
     if (ws.total_bytes > ws_bytes) return DIF_ENOSPACE;
-    ws.g.c = radius / (float)rings * 1.002f;    // ring `rings` then bounds every unvisited point beyond the radius (see k_cloud_query)
+    ws.g.c = radius / (float)rings * 1.002f;    // ring `rings` then bounds every unvisited point beyond the radius; far from the origin ring `rings` + 1 does (k_cloud_query)
     ws.g.inv_c = 1.0f / ws.g.c;
     // the table (key = empty, count - 1 = -1) and the rows (original index -1 = unused row) are adjacent: one all-ones fill
     if (hipMemsetAsync(ws.g.tab, 0xFF, (size_t)((char*)ws.g.sorted - (char*)ws.g.tab) + ws.sorted_bytes, s) != hipSuccess) return DIF_ELAUNCH;

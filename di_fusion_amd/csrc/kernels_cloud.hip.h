@@ -185,8 +185,20 @@ __device__ inline Row3 smallest_eigenvector(Row3 m0, Row3 m1, Row3 m2) {
     // pick order of the reference: c02 replaces c01 when longer; c12 wins whenever it is longer than the better of those two
     const bool take02 = n02 > n01;
     const bool take12 = n12 > (take02 ? n02 : n01);
-    const Row3 c = take12 ? c12 : (take02 ? c02 : c01);
-    const float len = sqrtf(take12 ? n12 : (take02 ? n02 : n01));
+    Row3 c = take12 ? c12 : (take02 ? c02 : c01);
+    float len2 = take12 ? n12 : (take02 ? n02 : n01);
+    // The squares that make up len2 leave float32's range long before the cross product does: an exactly collinear neighbourhood has lambda
+    // = a rounding error and a cross product of its size (len2 subnormal: a vector 20 ulp off unit length; len2 = 0: (NaN, NaN, -Inf), which
+    // is what the reference's formula returns there), and so has any cloud whose radius is below 1e-5 or above 1e5.  Outside [2^-100, 2^100]
+    // the product is rescaled by a power of two first (exact; inside that range it would change no bit, so it is not done); what is still
+    // outside afterwards — a zero vector, NaN — has no direction: NaN in all three components.
+    const float scale = len2 < 0x1p-100f ? 0x1p+80f : len2 > 0x1p+100f ? 0x1p-80f : 1.0f;
+    if (scale != 1.0f) {
+        c = Row3{c.x * scale, c.y * scale, c.z * scale};
+        len2 = norm2_3(c);
+    }
+    if (!(len2 >= 0x1p-100f && len2 <= 0x1p+100f)) return Row3{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+    const float len = sqrtf(len2);
     return Row3{c.x / len, c.y / len, c.z / len};
 }
 
@@ -213,21 +225,35 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_cloud_query(CloudGrid g, const fl
     int cx, cy, cz;
     cloud_cell(g, q.x, q.y, q.z, cx, cy, cz);
     const float r2 = radius * radius;
+    // How far a point can lie outside the box that its integer cell stands for, in float32 (u = 2^-24).  A point p is in cell j when
+    // floor(fl(p.x * inv_c)) == j with inv_c = fl(1 / c): fl(p.x * inv_c) = (p.x / c)(1 + e), |e| <= 2u + u^2, so j c - 2.01 u |j| c <= p.x
+    // <= (j + 1) c + 2.01 u |j + 1| c.  The edge itself is computed as fl((float)j * c), off by u |j| c, and the gap fl(edge - q.x) by u times
+    // itself.  A box test or a ring bound compares the query with a cell at most max_ring + 1 cells from its own, so every |j| c involved is
+    // below m = max |q| + (max_ring + 2) c, and the true gap is at least the computed one minus 4.02 u m (box test: the other cell's
+    // membership, its edge, the subtraction) or 6.03 u m (ring bound: both cells' memberships, the product rho * c, the subtraction).  `slack`
+    // = 2^-21 m = 8 u m covers both and its own three roundings (3 u of itself).  It is 2e-6 c near the origin and half a cell at the accept
+    // limit of cloud_cell (|j| < 2^20 - 64), where a fixed margin of 1e-3 c gave way from about 2^14 cells on.
+    // Float32 rounding is monotonic, so once |p.x - q.x| >= hx holds for the true gap it holds for fl(p.x - q.x), and for the squares and sums
+    // of d2 against those of the bound, taken in the same order: a cell or a ring that the tests below skip holds no point with d2 < bound.
+    const float slack = 0x1p-21f * (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + (float)(max_ring + 2) * g.c);
     const uint4* __restrict__ tab4 = reinterpret_cast<const uint4*>(g.tab);
     int2* const run = s_run + threadIdx.x;
     TopK<K> top;
     top.init(k);
     const int lead = K - k;                                 // sentinel slots in front of the list
     int inside = 0;
-    for (int rho = 0; rho <= max_ring; ++rho) {
+    // Ring max_ring bounds every unvisited point beyond the radius while slack stays under the 0.002 max_ring cells that the host's cell size
+    // leaves (up to some 2^12 cells from the origin); farther out one more ring does, whose bound is at least (max_ring + 0.49) c > radius for
+    // every accepted point.  The loop ends through the `covered` test below, never through its own limit.
+    for (int rho = 0; rho <= max_ring + 1; ++rho) {
         int dx = -rho, dy = -rho, dz = -rho;               // the shell in the order of three nested loops, interior columns reduced to their end caps
         bool more = true;
         while (more) {
             uint4 ent[CLOUD_NB];
             int off[CLOUD_NB];
             // kNN / normals: a cell whose nearest corner is strictly farther than the k-th distance so far (ties go by index) is not looked up
-            // at all.  The cell's box from the integer coordinates, shrunk by the same 1e-3 c that the ring bound below allows for floor()
-            // rounding.  (For the outlier count the same test against the radius costs more than it saves: measured.)
+            // at all.  The cell's box from the integer coordinates, shrunk by `slack` (above), as the ring bound below is.
+            // (For the outlier count the same test against the radius costs more than it saves: measured.)
             const float far2 = top.kth();
 #pragma unroll
             for (int b = 0; b < CLOUD_NB; ++b) {
@@ -239,7 +265,6 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_cloud_query(CloudGrid g, const fl
                         const float gx = dx < 0 ? q.x - (float)(cx + dx + 1) * g.c : dx > 0 ? (float)(cx + dx) * g.c - q.x : 0.0f;
                         const float gy = dy < 0 ? q.y - (float)(cy + dy + 1) * g.c : dy > 0 ? (float)(cy + dy) * g.c - q.y : 0.0f;
                         const float gz = dz < 0 ? q.z - (float)(cz + dz + 1) * g.c : dz > 0 ? (float)(cz + dz) * g.c - q.z : 0.0f;
-                        const float slack = 1e-3f * g.c;
                         const float hx = fmaxf(gx - slack, 0.0f), hy = fmaxf(gy - slack, 0.0f), hz = fmaxf(gz - slack, 0.0f);
                         look = (hx * hx + hy * hy) + hz * hz <= far2;
                     }
@@ -308,13 +333,13 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_cloud_query(CloudGrid g, const fl
             }
             if (MODE == CLOUD_OUTLIER && inside >= k) break;
         }
+        const float lb = (float)rho * g.c - slack;         // every unvisited point is at least this far
+        const bool covered = lb > 0.0f && r2 <= lb * lb;   // ... which puts all of them outside the radius: the list / the count is complete
         if (MODE == CLOUD_OUTLIER) {
-            if (inside >= k) break;                        // decided: at least k points inside the radius
-            continue;                                      // (ring max_ring covers the radius: the count is complete when the loop ends)
+            if (inside >= k || covered) break;             // decided: at least k points inside the radius, or all of them counted
+            continue;
         }
-        const float kth = top.kth();
-        const float lb = ((float)rho - 1e-3f) * g.c;       // every unvisited point is at least this far (1e-3: floor() rounding)
-        if (lb > 0.0f && kth < lb * lb) break;             // (the host sizes c so that ring max_ring covers the radius)
+        if (covered || (lb > 0.0f && top.kth() < lb * lb)) break;
     }
     if (MODE == CLOUD_KNN) {
 #pragma unroll

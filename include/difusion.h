@@ -245,8 +245,12 @@ int dif_point_box_filter(const float* points, const float* normals, int64_t N, f
  * (nearestKernel, :1070; squared L2 of CudaL2::dist, :1152-1155; results ascending by distance).  Here the index is a hashed
  * uniform grid living in the caller's workspace and the search is exact below `radius`: among the k nearest points of a
  * query (itself included, order (d2, index)), every one with d2 < radius^2 is reported exactly; the others as idx -1,
- * dist +inf.  pc is (n, stride) with stride 3 or 4 (the tracker passes xyz0 rows); 1 <= k <= 32.  Points with a non-finite
- * coordinate have no neighbours and are nobody's neighbour. */
+ * dist +inf.  pc is (n, stride) with stride 3 or 4 (the tracker passes xyz0 rows); 1 <= k <= 32; 0 < radius < 1e6.
+ * ACCEPTED COORDINATES: a point takes part when |floorf(x * (1 / c))| < 2^20 - 64 on every axis, where c = radius / rings * 1.002f and
+ * rings is 2 (dif_knn, dif_estimate_normals) or 1 (dif_remove_radius_outlier) for n <= 131072, 4 or 2 above.  So every point with
+ * |x|, |y|, |z| <= 262144 * radius is accepted by all three ops at every n, and results are exact for every accepted point wherever it
+ * lies in that range.  A point that is not accepted (farther out, NaN, Inf) has no neighbours and is nobody's neighbour: its rows are
+ * idx -1 / dist +inf, its mask 0, its normal NaN, and no other point's list names it. */
 int64_t dif_cloud_workspace_bytes(int64_t n);
 int dif_knn(const float* pc, int64_t n, int32_t stride, int32_t k, float radius, int32_t* out_idx, float* out_dist, void* workspace,
             int64_t workspace_bytes, void* stream);
@@ -255,7 +259,10 @@ int dif_knn(const float* pc, int64_t n, int32_t stride, int32_t k, float radius,
 int dif_remove_radius_outlier(const float* pc, int64_t n, int32_t stride, int32_t nb_points, float radius, uint8_t* out_mask,
                               void* workspace, int64_t workspace_bytes, void* stream);
 /* ext/pcproc/pcproc.cu:107-158,188-209 estimate_normals: PCA normal over neighbours 1..max_nn-1 of the sorted kNN list while
- * inside `radius` (fewer than 5 -> NaN), eigenvector by pcproc.cu:21-96, oriented towards cam_xyz (host float[3]). */
+ * inside `radius` (fewer than 5 -> NaN), eigenvector by pcproc.cu:21-96, oriented towards cam_xyz (host float[3]).  A row is either a
+ * unit vector or NaN in all three components, never Inf: where the reference's formula normalises a cross product whose squared length
+ * has left float32's range (exactly collinear neighbourhoods, radii below 1e-5 or above 1e5) the product is rescaled by a power of two
+ * first, and a neighbourhood without any direction (all points coincident, an isotropic covariance) gives NaN. */
 int dif_estimate_normals(const float* pc, int64_t n, int32_t stride, int32_t max_nn, float radius, const float* cam_xyz,
                          float* out_normals, void* workspace, int64_t workspace_bytes, void* stream);
 
