@@ -101,6 +101,11 @@ class DifRasterArgs(ctypes.Structure):
                 ("height", c_int32), ("width", c_int32), ("cull_backfaces", c_int32)]
 
 
+class DifSimplifyArgs(ctypes.Structure):
+    """include/difusion.h: dif_simplify_args_t"""
+    _fields_ = [("origin", c_float * 3), ("cell", c_float)]
+
+
 class DifColourArgs(ctypes.Structure):
     """include/difusion.h: dif_colour_args_t"""
     _fields_ = [("depth_tol", c_float), ("min_cos2", c_float), ("edge_gate", c_int32), ("reserved", c_int32)]
@@ -121,6 +126,9 @@ WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 
 COMP_COMPONENTS, COMP_STATUS, COMP_COUNT = 0, 1, 4                                                     # DIF_COMP_*
 SELECT_VERTICES, SELECT_TRIANGLES, SELECT_STATUS, SELECT_COUNT = 0, 1, 2, 4                            # DIF_SELECT_*
 EDGE_MAX_USE, EDGE_STATUS, EDGE_COUNT = 0, 1, 4                                                        # DIF_EDGE_*
+(SIMPLIFY_VERTICES, SIMPLIFY_TRIANGLES, SIMPLIFY_UNKEYED, SIMPLIFY_COLLAPSED, SIMPLIFY_DUPLICATE, SIMPLIFY_ISOLATED, SIMPLIFY_BAD_STD, SIMPLIFY_FLAT,
+ SIMPLIFY_STATUS) = range(9)                                                                           # DIF_SIMPLIFY_*
+SIMPLIFY_COUNT = 16
 MESH_STATUS_BAD_INDEX, MESH_STATUS_RUNAWAY, MESH_STATUS_TABLE_FULL = 1, 2, 4                           # DIF_MESH_STATUS_*
 RASTER_PIXELS_HIT, RASTER_DRAWN, RASTER_CLIPPED, RASTER_DEGENERATE, RASTER_CULLED, RASTER_OFFSCREEN, RASTER_LARGE, RASTER_STATUS, RASTER_COUNT = range(9)   # DIF_RASTER_*
 RASTER_THREAD_PIXELS = 64                                                                              # DIF_RASTER_THREAD_PIXELS
@@ -176,6 +184,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_mesh_edge_census_workspace_bytes": (c_int64, [c_int64]),
     "dif_mesh_edge_census": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_simplify_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dif_mesh_simplify": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(DifSimplifyArgs), c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dif_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     "dif_mesh_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),

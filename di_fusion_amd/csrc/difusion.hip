@@ -150,6 +150,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_cloud.hip.h"
 #include "kernels_weld.hip.h"
 #include "kernels_components.hip.h"
+#include "kernels_simplify.hip.h"
 #include "kernels_raster.hip.h"
 #include "kernels_colour.hip.h"
 #include "kernels_optimize.hip.h"
@@ -1879,6 +1880,122 @@ int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const i
     hipLaunchKernelGGL(k_edge_insert, dim3(mesh_blocks(3 * K)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)triangles, (int)(3 * K), (int)V, counts);
     hipLaunchKernelGGL(k_edge_slots, dim3(mesh_blocks(ws.cap, CENSUS_SLOT_ITEMS)), dim3(DIF_BLOCK), 0, s, ws.t, (const int*)vertex_component, (int)C, comp_edges, comp_boundary, counts);
     DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- simplifying an indexed mesh by vertex clustering ---------------------------------------------------------------
+extern "C++" {
+struct SimplifyWs {
+    SimplifyTable t;
+    SimplifyTriTable d;
+    int* rep;                       // [V]  table slot after the insert, lowest member of the cluster after k_simplify_sums
+    int* used;                      // [V]
+    int* cluster_out;               // [V]  output vertex of a used rep
+    unsigned long long* gsum;       // [V][SIMPLIFY_SUMS]
+    unsigned long long* csum;       // [V][4]
+    long long* nsum;                // [V][3]
+    int* tri_state;                 // [K]
+    int* block_tmp;                 // [4096]
+    size_t table_bytes;             // keys and minima are adjacent: one all-ones fill
+    size_t zero_bytes;              // used, gsum and csum are adjacent: one zero fill
+    size_t tri_table_bytes;
+    int64_t total_bytes;
+};
+
+static int carve_simplify(int64_t V, int64_t K, void* base, SimplifyWs& ws) {
+    if (!mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    int64_t cap = 64, dcap = 64;
+    int bits = 6, dbits = 6;
+    while (cap < 2 * V) { cap <<= 1; ++bits; }           // never more than half full (cap <= 2^32: the slot index and the probe bound fit 32 bits)
+    while (dcap < 2 * K) { dcap <<= 1; ++dbits; }
+    const size_t nv = (size_t)(V > 0 ? V : 1), nk = (size_t)(K > 0 ? K : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_key = take((size_t)cap * 8), o_min = take((size_t)cap * 4), o_tri = take((size_t)dcap * 4), o_rep = take(nv * 4), o_out = take(nv * 4);
+    const size_t o_used = take(nv * 4), o_gsum = take(nv * SIMPLIFY_SUMS * 8), o_csum = take(nv * 4 * 8), o_nsum = take(nv * 3 * 8);
+    const size_t o_state = take(nk * 4), o_tmp = take(4096 * 4);
+    ws.table_bytes = o_tri - o_key;
+    ws.tri_table_bytes = (size_t)dcap * 4;
+    ws.zero_bytes = o_nsum - o_used;
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.t.key = (unsigned long long*)(b + o_key);
+        ws.t.min_vertex = (unsigned*)(b + o_min);
+        ws.t.mask = (unsigned)(cap - 1);
+        ws.t.shift = 64 - bits;
+        ws.d.tri = (unsigned*)(b + o_tri);
+        ws.d.mask = (unsigned)(dcap - 1);
+        ws.d.shift = 64 - dbits;
+        ws.rep = (int*)(b + o_rep);
+        ws.cluster_out = (int*)(b + o_out);
+        ws.used = (int*)(b + o_used);
+        ws.gsum = (unsigned long long*)(b + o_gsum);
+        ws.csum = (unsigned long long*)(b + o_csum);
+        ws.nsum = (long long*)(b + o_nsum);
+        ws.tri_state = (int*)(b + o_state);
+        ws.block_tmp = (int*)(b + o_tmp);
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_simplify_workspace_bytes(int64_t V, int64_t K) {
+    SimplifyWs ws;
+    if (carve_simplify(V, K, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_simplify(const float* vertices, const float* vertex_std, const int32_t* triangles, const int64_t* triangle_id, int64_t V, int64_t K,
+                      const uint8_t* colour_rgb8, const float* colour_weight, const dif_simplify_args_t* args, void* workspace, int64_t workspace_bytes,
+                      float* out_vertices, float* out_normals, float* out_vertex_std, int32_t* out_triangles, int64_t* out_triangle_id,
+                      uint64_t* out_colour_accum, int32_t* vertex_cluster, int32_t* counts, void* stream) {
+    if (!args || !counts || !mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    if (!(args->cell > 0.0f) || __builtin_isinf(args->cell)) return DIF_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (!__builtin_isfinite(args->origin[k])) return DIF_EINVAL;
+    if ((colour_rgb8 == nullptr) != (colour_weight == nullptr) || (colour_rgb8 && !out_colour_accum)) return DIF_EINVAL;
+    if (V > 0 && (!vertices || !vertex_std || !out_vertices || !out_normals || !out_vertex_std || !vertex_cluster)) return DIF_EINVAL;
+    if (K > 0 && (!triangles || !triangle_id || !out_triangles || !out_triangle_id)) return DIF_EINVAL;
+    SimplifyWs ws;
+    if (V > 0 || K > 0) {
+        if (!workspace || ((uintptr_t)workspace & 15) != 0 || carve_simplify(V, K, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_SIMPLIFY_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (V == 0 && K == 0) return DIF_OK;
+    const dim3 block(DIF_BLOCK), per_vertex(mesh_blocks(V > 0 ? V : 1)), per_triangle(mesh_blocks(K > 0 ? K : 1));
+    const SimplifyGeo g{(double)args->origin[0], (double)args->origin[1], (double)args->origin[2], (double)args->cell};
+    if (V > 0) {
+        if (hipMemsetAsync(ws.t.key, 0xFF, ws.table_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+        if (hipMemsetAsync(ws.used, 0, ws.zero_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+        hipLaunchKernelGGL(k_simplify_insert, per_vertex, block, 0, s, ws.t, g, vertices, (int)V, ws.rep, counts);
+        hipLaunchKernelGGL(k_simplify_sums, dim3(mesh_blocks(V, SIMPLIFY_SUM_ITEMS)), block, 0, s, ws.t, g, vertices, vertex_std, colour_rgb8, colour_weight, (int)V, ws.rep, ws.gsum, ws.csum, counts);
+        DIF_CHECK_LAUNCH();
+    }
+    if (K > 0) {
+        // (V = 0: every index is out of range — k_simplify_classify reports it and dereferences nothing)
+        if (hipMemsetAsync(ws.d.tri, 0xFF, ws.tri_table_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+        hipLaunchKernelGGL(k_simplify_classify, per_triangle, block, 0, s, ws.d, (const int*)triangles, (const int*)ws.rep, (int)K, (int)V, ws.tri_state, counts);
+        hipLaunchKernelGGL(k_simplify_mark, dim3(mesh_blocks(K, SIMPLIFY_MARK_ITEMS)), block, 0, s, ws.d, (const int*)triangles, (const int*)ws.rep, (int)K, ws.tri_state, ws.used, counts);
+        DIF_CHECK_LAUNCH();
+    }
+    if (V > 0) {
+        SimplifyVertexFunctor fv{g, ws.rep, ws.used, vertices, vertex_std, ws.gsum, ws.csum, out_vertices, out_vertex_std,
+                                 colour_rgb8 ? (unsigned long long*)out_colour_accum : nullptr, ws.nsum, ws.cluster_out, counts};
+        if (launch_scan(fv, nullptr, (int)V, V, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+        hipLaunchKernelGGL(k_simplify_clusters, per_vertex, block, 0, s, (const int*)ws.rep, (const int*)ws.used, (const int*)ws.cluster_out, (int)V, vertex_cluster, counts);
+        DIF_CHECK_LAUNCH();
+    }
+    if (K > 0) {
+        SimplifyTriangleFunctor ft{ws.tri_state, (const int*)triangles, ws.rep, ws.cluster_out, triangle_id, out_vertices, out_triangles, out_triangle_id, ws.nsum,
+                                   1.0f / args->cell, counts};
+        if (launch_scan(ft, nullptr, (int)K, K, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+    }
+    if (V > 0) {
+        hipLaunchKernelGGL(k_weld_normals, per_vertex, block, 0, s, (const long long*)ws.nsum, (const int*)counts, out_normals);
+        DIF_CHECK_LAUNCH();
+    }
     return DIF_OK;
 }
 

@@ -631,12 +631,15 @@ class DenseIndexedMap:
         o = self._cache_out
         return o[0][:n], o[1][:n], o[2][:n]
 
-    def indexed_mesh(self, voxel_resolution: int = None, min_component_triangles: int = 0):
+    def indexed_mesh(self, voxel_resolution: int = None, min_component_triangles: int = 0, simplify_cell: float = 0.0):
         """The mesh cache as an indexed mesh (`system.mesh.IndexedMesh`: shared vertices, area-weighted vertex normals, int32 triangles),
         welded on the GPU by the lattice edge a vertex sits on (DESIGN.md "Indexed mesh").  `voxel_resolution`: the resolution the cache was
         extracted at (default: that of the last extract); corners that are not on that lattice stay unwelded and are counted
         (`counts["unkeyed"]`).  `min_component_triangles` > 0: without the connected components of fewer triangles (the fragments a fused
-        map carries beside its surfaces; `IndexedMesh.remove_small_components`).  None while the cache is empty."""
+        map carries beside its surfaces; `IndexedMesh.remove_small_components`).  `simplify_cell` > 0 (world units): after that cull, the
+        mesh simplified by vertex clustering on cubes of that edge (`IndexedMesh.simplify`).  The grid's origin is bound_min minus HALF A
+        LATTICE STEP per axis (float32; the step is voxel_size / resolution), so that the two fixed coordinates of a lattice-edge vertex sit in
+        the middle of a cell-boundary interval, not on a boundary; the result's `counts["origin"]` records it.  None while the cache is empty."""
         from . import mesh as mesh_mod
         t = self.mesh_cache_tensors()
         if t is None:
@@ -645,7 +648,12 @@ class DenseIndexedMap:
             voxel_resolution = self._xbuf[0][0]
         with torch.cuda.device(self.device):
             m = mesh_mod.weld(t[0], t[2], t[1], list(self._cmap.bound_min), float(self._cmap.voxel_size), int(voxel_resolution), self.n_xyz)
-            return m.remove_small_components(min_component_triangles) if min_component_triangles > 0 else m
+            m = m.remove_small_components(min_component_triangles) if min_component_triangles > 0 else m
+            if simplify_cell > 0:
+                step = np.float32(self._cmap.voxel_size) / np.float32(int(voxel_resolution))
+                origin = np.asarray(list(self._cmap.bound_min), dtype=np.float32) - step / np.float32(2)
+                m = m.simplify(float(simplify_cell), [float(x) for x in origin])
+            return m
 
     def render_view(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False, mesh=None,
                     min_component_triangles: int = 0):
@@ -668,7 +676,8 @@ class DenseIndexedMap:
         map's device; `gates` are the keywords of `system.mesh.colour_args` (depth_tol, min_cos, edge_gate).  Every view is splatted onto the
         vertices through the rasteriser, then the sums are resolved: `colors` (V,3) uint8, `color_weight` (V,), `counts["coloured"]`; a vertex
         that no view saw with at least `min_weight` stays grey (DESIGN.md "Colouring an indexed mesh").  The map keeps no keyframes: they are
-        the caller's to keep (`tracker.all_pd_pose` has the poses).  None while the cache is empty."""
+        the caller's to keep (`tracker.all_pd_pose` has the poses).  A smaller coloured mesh: `map.coloured_mesh(views).simplify(cell)` — the
+        clusters then carry the weighted mean of their members' colours.  None while the cache is empty."""
         mesh = self.indexed_mesh(voxel_resolution, min_component_triangles)
         if mesh is None:
             return None

@@ -4,7 +4,8 @@ its main loop as too slow).  The key rule and why the weld is not by position: D
 components, an edge census and the selection of a sub-mesh (`dif_mesh_components`, `dif_mesh_edge_census`, `dif_mesh_select`; DESIGN.md
 "Components of an indexed mesh").  And a look at it: depth, normal, std and triangle-index images from a camera pose (`dif_mesh_render`;
 DESIGN.md "Rendering an indexed mesh").  And its colour: RGB keyframes splatted onto the vertices through that rasteriser (`dif_mesh_colour_view`,
-`dif_mesh_colour_resolve`; DESIGN.md "Colouring an indexed mesh").
+`dif_mesh_colour_resolve`; DESIGN.md "Colouring an indexed mesh").  And a smaller one: vertex clustering on a grid (`dif_mesh_simplify`; DESIGN.md
+"Simplifying an indexed mesh").
 """
 from __future__ import annotations
 
@@ -25,7 +26,8 @@ class IndexedMesh:
     kept, triangles dropped (a repeated index after welding), unkeyed soup corners (not on the lattice: each a vertex of its own), status.
     A mesh derived from another carries its own vertices, triangles and status (`select`) and `components_removed` on top
     (`remove_small_components`).  A coloured one (`colourer().resolve()`) carries `colors` (V,3) uint8 and `color_weight` (V,) f32 as well, and
-    `counts["coloured"]`; both are None otherwise."""
+    `counts["coloured"]`; both are None otherwise.  A simplified one (`simplify`) carries `vertex_cluster` (V of the source,) i32 — the output
+    vertex of every source vertex, or -1 — and in `counts` the classes of `SIMPLIFY_COUNT_NAMES`, `cell` and `origin`; it is None otherwise."""
 
     def __init__(self, vertices, normals, vertex_std, triangles, triangle_flatten_id, counts: dict, colors=None, color_weight=None):
         self.vertices = vertices
@@ -36,11 +38,14 @@ class IndexedMesh:
         self.counts = dict(counts)
         self.colors = colors
         self.color_weight = color_weight
+        self.vertex_cluster = None
 
     def cpu(self) -> "IndexedMesh":
-        return IndexedMesh(self.vertices.cpu(), self.normals.cpu(), self.vertex_std.cpu(), self.triangles.cpu(), self.triangle_flatten_id.cpu(),
-                           self.counts, None if self.colors is None else self.colors.cpu(),
-                           None if self.color_weight is None else self.color_weight.cpu())
+        m = IndexedMesh(self.vertices.cpu(), self.normals.cpu(), self.vertex_std.cpu(), self.triangles.cpu(), self.triangle_flatten_id.cpu(),
+                        self.counts, None if self.colors is None else self.colors.cpu(),
+                        None if self.color_weight is None else self.color_weight.cpu())
+        m.vertex_cluster = None if self.vertex_cluster is None else self.vertex_cluster.cpu()
+        return m
 
     def components(self) -> "MeshComponents":
         """Connected components (`components`): per vertex, per triangle, and the size of each."""
@@ -76,6 +81,14 @@ class IndexedMesh:
         tc = c.triangle_component.long()
         mask = (tc >= 0) & keep[tc.clamp(min=0)] if c.count > 0 else torch.zeros_like(tc, dtype=torch.bool)
         return _select(self, mask, c.count - (keep & (c.n_triangles > 0)).sum().to(torch.int32))
+
+    def simplify(self, cell: float, origin: Sequence[float] = (0.0, 0.0, 0.0)) -> "IndexedMesh":
+        """A smaller mesh by vertex clustering (`simplify`): the vertices inside one cube of edge `cell` (world units) of the grid through `origin`
+        become their mean, triangles that collapse or repeat go, normals are recomputed.  Colours travel along when the mesh has them: the
+        weighted mean of a cluster, resolved with `colour_resolve(min_weight=0)`.  The result carries `vertex_cluster` and, in `counts`, the
+        classes, `cell` and `origin` (as the float32 the kernel saw).  Vertex clustering preserves neither manifoldness nor genus, places no
+        vertex by a quadric, and fuses thin double-sided sheets closer than a cell."""
+        return simplify(self.vertices, self.vertex_std, self.triangles, self.triangle_flatten_id, cell, origin, self.colors, self.color_weight)
 
     def render(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> "MeshRender":
         """Depth, normal, std and triangle-index images of this mesh from the camera-to-world `pose` (`render`)."""
@@ -305,6 +318,77 @@ def _select(m: IndexedMesh, keep: torch.Tensor, components_removed: Optional[tor
     if components_removed is not None:
         out["components_removed"] = c[_lib.SELECT_COUNT]
     return IndexedMesh(out_v[:nv], out_n[:nv], out_s[:nv], out_t[:nk], out_i[:nk], out)
+
+
+# ---- simplification (DESIGN.md "Simplifying an indexed mesh") --------------------------------------------------------------------------
+SIMPLIFY_COUNT_NAMES = ("vertices", "triangles", "unkeyed", "collapsed", "duplicate", "isolated", "bad_std", "flat", "status")
+
+
+def simplify_args(cell: float, origin: Sequence[float] = (0.0, 0.0, 0.0)) -> _lib.DifSimplifyArgs:
+    a = _lib.DifSimplifyArgs()
+    if isinstance(origin, torch.Tensor):
+        origin = origin.detach().cpu().tolist()
+    if len(origin) != 3:
+        raise ValueError(f"simplify: origin must have three components; got {len(origin)}")
+    for k in range(3):
+        a.origin[k] = float(origin[k])
+    a.cell = float(cell)
+    if not (a.cell > 0.0 and np.isfinite(a.cell)) or not all(np.isfinite(a.origin[k]) for k in range(3)):
+        raise ValueError(f"simplify: cell must be positive and finite, origin finite (as float32); got {cell}, {tuple(origin)}")
+    return a
+
+
+def simplify(vertices: torch.Tensor, vertex_std: torch.Tensor, triangles: torch.Tensor, triangle_flatten_id: torch.Tensor, cell: float,
+             origin: Sequence[float] = (0.0, 0.0, 0.0), colors: Optional[torch.Tensor] = None, color_weight: Optional[torch.Tensor] = None) -> IndexedMesh:
+    """The flat operator: the arrays of an indexed mesh on the GPU -> the `IndexedMesh` of its vertex clusters on the grid of cubes of edge
+    `cell` through `origin` (`dif_mesh_simplify`, include/difusion.h has the contract).  `colors` (V,3) uint8 and `color_weight` (V,) f32, both
+    or neither: the result then carries the weighted cluster means as `colors` / `color_weight` and `counts["coloured"]`.  `counts`: the names of
+    `SIMPLIFY_COUNT_NAMES` (status may hold `_lib.MESH_STATUS_BAD_INDEX`: such triangles are dropped), `cell` and `origin` as the float32 values
+    the kernel saw; `vertex_cluster` (V,) i32 on the result.  One synchronisation (the counts), a second one with colours."""
+    K = _check_triangles(triangles, "simplify")
+    _lib.require_cuda(vertices, vertex_std, triangle_flatten_id, colors, color_weight)
+    V = int(vertices.shape[0])
+    if vertices.dtype != torch.float32 or vertex_std.dtype != torch.float32 or triangle_flatten_id.dtype != torch.int64:
+        raise RuntimeError("simplify: vertices and vertex_std must be float32, triangle_flatten_id int64")
+    if tuple(vertices.shape) != (V, 3) or tuple(vertex_std.shape) != (V,) or tuple(triangle_flatten_id.shape) != (K,):
+        raise RuntimeError(f"simplify: expected (V,3), (V,), (K,3), (K,); got {tuple(vertices.shape)}, {tuple(vertex_std.shape)}, "
+                           f"{tuple(triangles.shape)}, {tuple(triangle_flatten_id.shape)}")
+    if (colors is None) != (color_weight is None):
+        raise ValueError("simplify: colors and color_weight go together: both or neither")
+    if colors is not None and (colors.dtype != torch.uint8 or tuple(colors.shape) != (V, 3) or color_weight.dtype != torch.float32 or
+                               tuple(color_weight.shape) != (V,)):
+        raise RuntimeError(f"simplify: colors must be ({V},3) uint8 and color_weight ({V},) float32; got {tuple(colors.shape)} {colors.dtype}, "
+                           f"{tuple(color_weight.shape)} {color_weight.dtype}")
+    args = simplify_args(cell, origin)
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_simplify_workspace_bytes(V, K))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_simplify cannot index {V} vertices, {K} triangles (V and 3 K must stay below 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        out_v = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        out_n = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        out_s = torch.empty((V,), dtype=torch.float32, device=dev)
+        out_t = torch.empty((K, 3), dtype=torch.int32, device=dev)
+        out_i = torch.empty((K,), dtype=torch.int64, device=dev)
+        accum = colour_accumulator(V, dev) if colors is not None else None
+        cluster = torch.empty((V,), dtype=torch.int32, device=dev)
+        counts = torch.empty((_lib.SIMPLIFY_COUNT,), dtype=torch.int32, device=dev)
+        _lib.check(lib.dif_mesh_simplify(_lib.ptr(vertices), _lib.ptr(vertex_std), _lib.ptr(triangles), _lib.ptr(triangle_flatten_id), V, K, _lib.ptr(colors),
+                                         _lib.ptr(color_weight), ctypes.byref(args), _lib.ptr(ws), ws_bytes, _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_s),
+                                         _lib.ptr(out_t), _lib.ptr(out_i), _lib.ptr(accum), _lib.ptr(cluster), _lib.ptr(counts), _lib.stream_ptr()),
+                   "dif_mesh_simplify")
+        c = counts.cpu().tolist()
+        _check_status(c[_lib.SIMPLIFY_STATUS], "dif_mesh_simplify")
+        nv, nk = c[_lib.SIMPLIFY_VERTICES], c[_lib.SIMPLIFY_TRIANGLES]
+        out = dict(zip(SIMPLIFY_COUNT_NAMES, c[:len(SIMPLIFY_COUNT_NAMES)]), cell=float(args.cell), origin=tuple(float(args.origin[k]) for k in range(3)))
+        col = weight = None
+        if accum is not None:
+            col, weight, out["coloured"] = colour_resolve(accum[:nv], 0.0)
+    m = IndexedMesh(out_v[:nv], out_n[:nv], out_s[:nv], out_t[:nk], out_i[:nk], out, col, weight)
+    m.vertex_cluster = cluster
+    return m
 
 
 # ---- rendering (DESIGN.md "Rendering an indexed mesh") ---------------------------------------------------------------------------------

@@ -474,6 +474,43 @@ int64_t dif_mesh_edge_census_workspace_bytes(int64_t K);
 int dif_mesh_edge_census(const int32_t* triangles, int64_t K, int64_t V, const int32_t* vertex_component, int64_t C, void* workspace,
                          int64_t workspace_bytes, int32_t* comp_edges, int32_t* comp_boundary, int32_t* counts, void* stream);
 
+/* Simplify an indexed mesh by vertex clustering on a grid (no reference counterpart; DESIGN.md "Simplifying an indexed mesh").
+ * Every sum is an integer and every numbering follows the lowest id, so the output is a pure function of the input.
+ * CLUSTER of a vertex, in double, every operation rounded once: per axis t = ((double) p - (double) origin) / (double) cell, c = floor(t).
+ * The vertex is keyed when all three t are finite and all three c lie in [0, 2^21); its cluster is the triple c (packed into 63 bits).  A
+ * vertex that is not keyed is a cluster of its own (counted in UNKEYED): its position and std are copied bit for bit.
+ * ATTRIBUTES of a cluster of keyed vertices.  Position, per axis: S = the int64 sum of llrint((t - c) 65536.0) over its n members;
+ *   out = (float) ((double) origin + ((double) c + ((double) S / (double) n) / 65536.0) * (double) cell), in exactly that order.
+ * Std: a member with a finite std >= 0 adds llrint(fmin((double) std, 64.0) 2^24) (the sum stays below 2^61 for V < 2^31); the others are left
+ *   out and counted in BAD_STD; out = (float) (((double) S / (double) m) / 2^24) over the m valid members, the quiet NaN 0x7FC00000 when m = 0.
+ * Colour, when colour_rgb8 ((V,3) u8) and colour_weight ((V) f32) are given: a vertex, keyed or not, adds w r, w g, w b, w to its cluster's row
+ *   of out_colour_accum ((V,4) u64, the layout of dif_mesh_colour_view's accumulator; rows of output vertices are overwritten, not added to),
+ *   w = (uint64) llrint(fmin(fmax((double) weight, 0), 2^24) 65536.0), 0 for a weight that is not finite.  dif_mesh_colour_resolve turns the rows into colours: a cluster whose
+ *   members share one colour keeps it exactly (a vertex on its own: whenever its w >= 1).
+ * TRIANGLES are kept in input order, corners in their order, with remapped indices and their triangle_id.  A triangle is dropped, and falls
+ * into exactly one class, tested in this order: an index outside [0, V) (status bit DIF_MESH_STATUS_BAD_INDEX, never dereferenced; not counted
+ * otherwise); COLLAPSED: two corners in one cluster; DUPLICATE: the same remapped triple — after rotating it so that its smallest index comes
+ * first, orientation kept — as a triangle of lower input index (the lowest stays; an oppositely oriented copy is another triangle and stays).
+ * OUTPUT VERTICES: the clusters that a kept triangle names, numbered in ascending order of their LOWEST MEMBER VERTEX ID; the other clusters
+ * are counted in ISOLATED.  vertex_cluster (V) i32: the output vertex of v, or -1.
+ * NORMALS are recomputed as dif_mesh_weld does it, from the output float32 positions, edges scaled by the float32 1.0f / cell: the float32
+ * cross product (each multiply and subtract rounded once), each component as llrint(c 2^30) into int64 sums, normalised in double, (0,0,0) for a
+ * zero sum.  A kept triangle with a cross component that is not finite or reaches 2^31 in magnitude stays, adds nothing and is counted in FLAT.
+ * counts (int32[DIF_SIMPLIFY_COUNT], device, cleared by the call): DIF_SIMPLIFY_* below; STATUS holds DIF_MESH_STATUS_* bits (TABLE_FULL cannot
+ * happen: both tables hold twice their elements; reported instead of looping).  kept + bad index + COLLAPSED + DUPLICATE = K.
+ * Outputs are sized (V,3), (V,3), (V), (K,3), (K); rows beyond the counts are not written.  V = 0 or K = 0 is valid: an empty mesh (with K = 0 every
+ * cluster is isolated).  DIF_EINVAL: cell not finite or <= 0, an origin that is not finite, V or 3 K >= 2^31 (the workspace size is then -1),
+ * exactly one of the two colour inputs, colour inputs without out_colour_accum, a NULL args or counts, a NULL array that V or K says is not
+ * empty, a workspace that is NULL, not aligned to 16 bytes, or smaller than dif_mesh_simplify_workspace_bytes. */
+typedef struct { float origin[3]; float cell; } dif_simplify_args_t;
+enum { DIF_SIMPLIFY_VERTICES = 0, DIF_SIMPLIFY_TRIANGLES = 1, DIF_SIMPLIFY_UNKEYED = 2, DIF_SIMPLIFY_COLLAPSED = 3, DIF_SIMPLIFY_DUPLICATE = 4,
+       DIF_SIMPLIFY_ISOLATED = 5, DIF_SIMPLIFY_BAD_STD = 6, DIF_SIMPLIFY_FLAT = 7, DIF_SIMPLIFY_STATUS = 8, DIF_SIMPLIFY_COUNT = 16 };
+int64_t dif_mesh_simplify_workspace_bytes(int64_t V, int64_t K);
+int dif_mesh_simplify(const float* vertices, const float* vertex_std, const int32_t* triangles, const int64_t* triangle_id, int64_t V, int64_t K,
+                      const uint8_t* colour_rgb8, const float* colour_weight, const dif_simplify_args_t* args, void* workspace, int64_t workspace_bytes,
+                      float* out_vertices, float* out_normals, float* out_vertex_std, int32_t* out_triangles, int64_t* out_triangle_id,
+                      uint64_t* out_colour_accum, int32_t* vertex_cluster, int32_t* counts, void* stream);
+
 /* Depth, normal, std and triangle-index images of an indexed mesh seen from a pinhole camera (DESIGN.md "Rendering an indexed mesh").
  * Pixel (u, v) is column and row, its centre sits at integer coordinates, x = (u - cx) / fx * z (dif_unproject's convention).
  * Camera point = world_to_cam (row-major 3x4, float32) applied as ((r0 x + r1 y) + r2 z) + t.  A vertex is valid when that point is finite,
