@@ -106,6 +106,11 @@ class DifSimplifyArgs(ctypes.Structure):
     _fields_ = [("origin", c_float * 3), ("cell", c_float)]
 
 
+class DifLocatorArgs(ctypes.Structure):
+    """include/difusion.h: dif_locator_args_t"""
+    _fields_ = [("cell", c_float), ("max_cells", c_int32), ("pair_capacity", c_int64)]
+
+
 class DifColourArgs(ctypes.Structure):
     """include/difusion.h: dif_colour_args_t"""
     _fields_ = [("depth_tol", c_float), ("min_cos2", c_float), ("edge_gate", c_int32), ("reserved", c_int32)]
@@ -130,6 +135,11 @@ EDGE_MAX_USE, EDGE_STATUS, EDGE_COUNT = 0, 1, 4                                 
  SIMPLIFY_STATUS) = range(9)                                                                           # DIF_SIMPLIFY_*
 SIMPLIFY_COUNT = 16
 MESH_STATUS_BAD_INDEX, MESH_STATUS_RUNAWAY, MESH_STATUS_TABLE_FULL = 1, 2, 4                           # DIF_MESH_STATUS_*
+MESH_STATUS_PAIR_OVERFLOW = 8
+LOCATOR_MAX_CELLS, LOCATOR_MAX_RATIO = 64, 60                                                          # DIF_LOCATOR_MAX_*
+(LOCATOR_INDEXED, LOCATOR_LARGE, LOCATOR_DEGENERATE, LOCATOR_SKIPPED, LOCATOR_BAD_INDEX, LOCATOR_PAIRS, LOCATOR_CELLS, LOCATOR_STATUS) = range(8)   # DIF_LOCATOR_*
+LOCATOR_COUNT = 8
+CLOSEST_FOUND, CLOSEST_FAR, CLOSEST_BAD_POINT, CLOSEST_STATUS, CLOSEST_COUNT = 0, 1, 2, 3, 4           # DIF_CLOSEST_*
 RASTER_PIXELS_HIT, RASTER_DRAWN, RASTER_CLIPPED, RASTER_DEGENERATE, RASTER_CULLED, RASTER_OFFSCREEN, RASTER_LARGE, RASTER_STATUS, RASTER_COUNT = range(9)   # DIF_RASTER_*
 RASTER_THREAD_PIXELS = 64                                                                              # DIF_RASTER_THREAD_PIXELS
 COLOUR_USED, COLOUR_NO_HIT, COLOUR_BAD_COLOUR, COLOUR_DEPTH, COLOUR_EDGE, COLOUR_GRAZING, COLOUR_STATUS, COLOUR_COUNT = 0, 1, 2, 3, 4, 5, 6, 8   # DIF_COLOUR_*
@@ -187,6 +197,10 @@ SIGNATURES = {
     "dif_mesh_simplify_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "dif_mesh_simplify": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(DifSimplifyArgs), c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_locator_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "dif_mesh_locator_build": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, POINTER(DifLocatorArgs), c_void_p, c_int64, c_void_p, c_void_p]),
+    "dif_mesh_closest": (c_int32, [POINTER(DifLocatorArgs), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
     "dif_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     "dif_mesh_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -151,6 +151,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_weld.hip.h"
 #include "kernels_components.hip.h"
 #include "kernels_simplify.hip.h"
+#include "kernels_closest.hip.h"
 #include "kernels_raster.hip.h"
 #include "kernels_colour.hip.h"
 #include "kernels_optimize.hip.h"
@@ -1996,6 +1997,103 @@ int dif_mesh_simplify(const float* vertices, const float* vertex_std, const int3
         hipLaunchKernelGGL(k_weld_normals, per_vertex, block, 0, s, (const long long*)ws.nsum, (const int*)counts, out_normals);
         DIF_CHECK_LAUNCH();
     }
+    return DIF_OK;
+}
+
+// ---- closest point on an indexed mesh ---------------------------------------------------------------------------------
+extern "C++" {
+struct LocatorWs { Locator L; int* block_tmp; int64_t T; size_t clear_bytes; int64_t total_bytes; };
+
+static bool locator_args_ok(const dif_locator_args_t* a) {
+    return a && a->cell > 0.0f && !__builtin_isinf(a->cell) && a->max_cells <= (1 << 20);
+}
+
+static int carve_locator(int64_t V, int64_t K, int64_t pair_capacity, void* base, LocatorWs& ws) {
+    if (!mesh_sizes_ok(V, K) || pair_capacity < 1 || pair_capacity >= ((int64_t)1 << 28)) return DIF_EINVAL;
+    int64_t T = 4096;
+    int bits = 12;
+    while (T < 2 * pair_capacity) { T <<= 1; ++bits; }   // distinct cells <= pairs <= capacity: never more than half full
+    const size_t nk = (size_t)(K > 0 ? K : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_head = take(LOC_H_WORDS * 4), o_tab = take((size_t)T * sizeof(CloudEntry)), o_refs = take((size_t)pair_capacity * 4);
+    const size_t o_rec = take(nk * 48), o_ncell = take(nk * 4), o_large = take(nk * 4), o_tmp = take(4096 * 4);
+    ws.T = T;
+    ws.clear_bytes = (size_t)T * sizeof(CloudEntry);
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.L.head = (int*)(b + o_head);
+        ws.L.g.tab = (CloudEntry*)(b + o_tab);
+        ws.L.g.sorted = nullptr;
+        ws.L.g.slot = nullptr;
+        ws.L.g.mask = (unsigned)(T - 1);
+        ws.L.g.shift = 64 - bits;
+        ws.L.refs = (int*)(b + o_refs);
+        ws.L.rec = (float4*)(b + o_rec);
+        ws.L.ncell = (int*)(b + o_ncell);
+        ws.L.large = (int*)(b + o_large);
+        ws.L.capacity = (int)pair_capacity;
+        ws.block_tmp = (int*)(b + o_tmp);
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_locator_workspace_bytes(int64_t V, int64_t K, int64_t pair_capacity) {
+    LocatorWs ws;
+    if (carve_locator(V, K, pair_capacity, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_locator_build(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, const dif_locator_args_t* args, void* workspace,
+                           int64_t workspace_bytes, int32_t* counts, void* stream) {
+    if (!locator_args_ok(args) || !counts) return DIF_EINVAL;
+    if ((V > 0 && !vertices) || (K > 0 && !triangles)) return DIF_EINVAL;
+    LocatorWs ws;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || carve_locator(V, K, args->pair_capacity, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes)
+        return DIF_EINVAL;
+    ws.L.g.c = args->cell;
+    ws.L.g.inv_c = 1.0f / args->cell;
+    hipStream_t s = (hipStream_t)stream;
+    // the header (zero) and the table (key = empty, count - 1 = -1)
+    if (hipMemsetAsync(ws.L.head, 0, LOC_H_WORDS * 4, s) != hipSuccess) return DIF_ELAUNCH;
+    if (hipMemsetAsync(ws.L.g.tab, 0xFF, ws.clear_bytes, s) != hipSuccess) return DIF_ELAUNCH;
+    if (K > 0) {
+        // (V = 0: every index is out of range — k_loc_classify reports it and dereferences nothing)
+        const dim3 block(DIF_BLOCK), per_triangle(mesh_blocks(K));
+        const int max_cells = args->max_cells == 0 ? DIF_LOCATOR_MAX_CELLS : args->max_cells;
+        hipLaunchKernelGGL(k_loc_classify, per_triangle, block, 0, s, ws.L, vertices, (const int*)triangles, (int)K, (int)V, max_cells);
+        hipLaunchKernelGGL(k_loc_insert, per_triangle, block, 0, s, ws.L, (int)K);
+        DIF_CHECK_LAUNCH();
+        CloudStartFunctor f{ws.L.g.tab};
+        if (launch_scan(f, nullptr, (int)ws.T, ws.T, ws.block_tmp, s) != DIF_OK) return DIF_ELAUNCH;
+        hipLaunchKernelGGL(k_loc_fill, per_triangle, block, 0, s, ws.L, (int)K);
+    }
+    hipLaunchKernelGGL(k_loc_finish, dim3(1), dim3(64), 0, s, ws.L, counts);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int dif_mesh_closest(const dif_locator_args_t* args, int64_t K, const void* workspace, int64_t workspace_bytes, const float* points, int64_t N,
+                     int32_t stride, float max_distance, float* out_d2, int32_t* out_triangle, float* out_point, float* out_barycentric,
+                     int32_t* counts, void* stream) {
+    if (!locator_args_ok(args) || !counts || N < 0 || N >= ((int64_t)1 << 31) || stride < 3) return DIF_EINVAL;
+    if (!(max_distance > 0.0f) || __builtin_isinf(max_distance) || (double)max_distance / (double)args->cell > (double)DIF_LOCATOR_MAX_RATIO) return DIF_EINVAL;
+    if (N > 0 && (!points || !out_d2 || !out_triangle || !out_point || !out_barycentric)) return DIF_EINVAL;
+    LocatorWs ws;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || carve_locator(0, K, args->pair_capacity, (void*)workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes)
+        return DIF_EINVAL;
+    ws.L.g.c = args->cell;
+    ws.L.g.inv_c = 1.0f / args->cell;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_CLOSEST_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    if (N == 0) return DIF_OK;
+    const int max_ring = (int)floor((double)max_distance / (double)args->cell) + 1;      // <= DIF_LOCATOR_MAX_RATIO + 1: offsets up to max_ring + 1 fit the ring encoding
+    const LocQueryOut out{out_d2, out_triangle, out_point, out_barycentric};
+    hipLaunchKernelGGL(k_loc_query, dim3(mesh_blocks(N)), dim3(DIF_BLOCK), 0, s, ws.L, (int)K, points, (int)N, (int)stride, max_distance * max_distance, max_ring, out,
+                       counts);
+    DIF_CHECK_LAUNCH();
     return DIF_OK;
 }
 

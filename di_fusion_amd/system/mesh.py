@@ -5,7 +5,8 @@ components, an edge census and the selection of a sub-mesh (`dif_mesh_components
 "Components of an indexed mesh").  And a look at it: depth, normal, std and triangle-index images from a camera pose (`dif_mesh_render`;
 DESIGN.md "Rendering an indexed mesh").  And its colour: RGB keyframes splatted onto the vertices through that rasteriser (`dif_mesh_colour_view`,
 `dif_mesh_colour_resolve`; DESIGN.md "Colouring an indexed mesh").  And a smaller one: vertex clustering on a grid (`dif_mesh_simplify`; DESIGN.md
-"Simplifying an indexed mesh").
+"Simplifying an indexed mesh").  And its distance to anything: the exact closest point on its surface for a cloud of points
+(`dif_mesh_locator_build`, `dif_mesh_closest`; DESIGN.md "Closest point on an indexed mesh").
 """
 from __future__ import annotations
 
@@ -89,6 +90,46 @@ class IndexedMesh:
         classes, `cell` and `origin` (as the float32 the kernel saw).  Vertex clustering preserves neither manifoldness nor genus, places no
         vertex by a quadric, and fuses thin double-sided sheets closer than a cell."""
         return simplify(self.vertices, self.vertex_std, self.triangles, self.triangle_flatten_id, cell, origin, self.colors, self.color_weight)
+
+    def locator(self, cell: Optional[float] = None) -> "MeshLocator":
+        """A `MeshLocator` over this mesh's surface (`locator`): build once, query with `.closest` as often as needed."""
+        return locator(self.vertices, self.triangles, cell)
+
+    def closest(self, points: torch.Tensor, max_distance: float, cell: Optional[float] = None) -> "MeshClosest":
+        """The closest point of this mesh's surface for every row of `points` (N,>=3) f32 within `max_distance` (`MeshLocator.closest`).  Builds a
+        locator for the one call: keep `self.locator()` when there are several clouds."""
+        return self.locator(cell).closest(points, max_distance)
+
+    def distance_to(self, other: "IndexedMesh", max_distance: float, cell: Optional[float] = None) -> dict:
+        """This mesh's VERTICES against `other`'s SURFACE: `d2` (V,) f32 on the device (inf where nothing of `other` lies within `max_distance`),
+        and `mean`, `rms`, `max`, `median` of the distance over the vertices that found a point, `found` and `far` (NaN figures when none did).
+        ONE-SIDED and VERTEX-SAMPLED: it does not see where `other` has surface that this mesh lacks, nor what happens inside this mesh's
+        triangles — call it both ways for a symmetric figure.  Unsigned.  The reductions run on the device; one read-back on top of the locator's.
+        `cell`: the cell of `other`'s locator; default: `default_locator_cell`, or max_distance / 59 where that is larger, so that any
+        `max_distance` stays within the ring limit (no answer depends on the cell)."""
+        if cell is None:
+            r = float(np.float32(max_distance))
+            cell = default_locator_cell(other.vertices, other.triangles)
+            if np.isfinite(r) and r > 0.0:
+                cell = max(cell, float(np.float32(r / (_lib.LOCATOR_MAX_RATIO - 1))))
+        c = other.locator(cell).closest(self.vertices, max_distance)
+        with torch.cuda.device(self.vertices.device):
+            d = torch.sqrt(c.d2[torch.isfinite(c.d2)]).double()
+            if d.numel() > 0:
+                stats = torch.stack([d.mean(), torch.sqrt((d * d).mean()), d.max(), d.median()]).cpu().tolist()
+            else:
+                stats = [float("nan")] * 4
+        return dict(d2=c.d2, mean=stats[0], rms=stats[1], max=stats[2], median=stats[3], found=c.counts["found"], far=c.counts["far"])
+
+    def interpolate(self, closest: "MeshClosest", values: torch.Tensor) -> torch.Tensor:
+        """A per-vertex attribute `values` (V,) or (V,C) f32 of THIS mesh at the closest points of `closest` (a result of this mesh's locator):
+        (b0 x0 + b1 x1) + b2 x2 per row with the barycentrics and the triangle's three vertices in index order, in float32 — what carries std,
+        normals or colours from one mesh to the points (or the vertices) of another.  Rows without a closest point are NaN."""
+        _lib.require_cuda(values, closest.triangle, closest.barycentric)
+        V = int(self.vertices.shape[0])
+        if values.dtype != torch.float32 or values.dim() not in (1, 2) or int(values.shape[0]) != V:
+            raise RuntimeError(f"interpolate: values must be ({V},) or ({V},C) float32; got {tuple(values.shape)} {values.dtype}")
+        return interpolate(self.triangles, closest.triangle, closest.barycentric, values)
 
     def render(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> "MeshRender":
         """Depth, normal, std and triangle-index images of this mesh from the camera-to-world `pose` (`render`)."""
@@ -595,3 +636,160 @@ class MeshColourer:
         m = self.mesh
         colors, weight, n = colour_resolve(self.accum, min_weight)
         return IndexedMesh(m.vertices, m.normals, m.vertex_std, m.triangles, m.triangle_flatten_id, dict(m.counts, coloured=n), colors, weight)
+
+
+# ---- closest point (DESIGN.md "Closest point on an indexed mesh") ----------------------------------------------------------------------
+LOCATOR_COUNT_NAMES = ("indexed", "large", "degenerate", "skipped", "bad_index", "pairs", "cells", "status")
+CLOSEST_COUNT_NAMES = ("found", "far", "bad_point", "status")
+
+
+def default_locator_cell(vertices: torch.Tensor, triangles: torch.Tensor) -> float:
+    """Twice the mean longest box side of the triangles whose indices are in range and whose vertices are finite (not only the usable ones:
+    a degenerate triangle counts, one beyond the key range too; no answer depends on the cell), from an INTEGER sum (sides in
+    units of 2^-20, rounded, summed in int64: the same on every run), as a float32 value; 1.0 when there is no such triangle.  Any cell gives
+    the same answers; this one keeps a triangle in about 2^3 cells or fewer.  One read-back."""
+    V = int(vertices.shape[0])
+    with torch.cuda.device(triangles.device):
+        t = triangles.long()
+        valid = ((t >= 0) & (t < V)).all(dim=1)
+        if V == 0 or t.shape[0] == 0:
+            return 1.0
+        p = vertices[torch.where(valid[:, None], t, torch.zeros_like(t))]            # (K, corner, axis)
+        side = (p.max(dim=1).values - p.min(dim=1).values).max(dim=1).values.double()
+        good = valid & torch.isfinite(side) & (side < 2.0 ** 40)
+        total = torch.round(torch.where(good, side, torch.zeros_like(side)) * 2.0 ** 20).long().sum()
+        total, n = torch.stack([total, good.sum()]).cpu().tolist()
+    cell = np.float32(2.0 * (float(total) / n) / 2.0 ** 20) if n else np.float32(1.0)
+    return float(cell) if cell > 0 else 1.0
+
+
+class MeshClosest:
+    """d2 (N,) f32 (inf: nothing within max_distance), triangle (N,) i32 (-1), point (N,3) f32 (NaN), barycentric (N,3) f32 (NaN; the weights
+    of the triangle's three vertices in index order) — device tensors, `.cpu()` for a host copy — `distance` = sqrt(d2), and `counts`: found,
+    far, bad_point (a query that is not finite or outside the grid's key range), status."""
+
+    def __init__(self, d2, triangle, point, barycentric, counts: dict):
+        self.d2 = d2
+        self.triangle = triangle
+        self.point = point
+        self.barycentric = barycentric
+        self.counts = dict(counts)
+
+    @property
+    def distance(self) -> torch.Tensor:
+        return torch.sqrt(self.d2)
+
+    def cpu(self) -> "MeshClosest":
+        return MeshClosest(self.d2.cpu(), self.triangle.cpu(), self.point.cpu(), self.barycentric.cpu(), self.counts)
+
+
+class MeshLocator:
+    """The grid over one mesh's triangles (`locator`): `workspace` (device bytes; it holds a copy of every usable triangle, so the mesh arrays
+    may go), `args`, `n_triangles`, and `counts`: triangles indexed / on the large list / degenerate / skipped (not finite, or outside the key
+    range) / bad_index, the (triangle, cell) pairs, the distinct cells, `cell` (the float32 the kernel saw), `max_cells`, status (may hold
+    `_lib.MESH_STATUS_BAD_INDEX`)."""
+
+    def __init__(self, workspace: torch.Tensor, args: _lib.DifLocatorArgs, n_triangles: int, counts: dict):
+        self.workspace = workspace
+        self.args = args
+        self.n_triangles = int(n_triangles)
+        self.counts = dict(counts)
+
+    def closest(self, points: torch.Tensor, max_distance: float) -> MeshClosest:
+        """points (N,3) or (N,>=3) f32 on the GPU (the first three columns are read: an (N,6) xyz + normal cloud goes as it is) -> `MeshClosest`:
+        per point the triangle that minimises (d2, triangle index) among those with d2 <= max_distance^2 — a point exactly at `max_distance` is
+        found.  The answer does not depend on the cell; the time grows with (max_distance / cell)^3 for points that find nothing, and depends on
+        how coherent the order of the points is.  One synchronisation (the counts)."""
+        _lib.require_cuda(points)
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3:
+            raise RuntimeError(f"closest: points must be (N,>=3) float32; got {tuple(points.shape)} {points.dtype}")
+        if points.device != self.workspace.device:
+            raise RuntimeError(f"closest: points live on {points.device}, the locator on {self.workspace.device}")
+        r = float(np.float32(max_distance))
+        if not (r > 0.0 and np.isfinite(r)):
+            raise ValueError(f"closest: max_distance must be positive and finite (as float32); got {max_distance}")
+        if r / float(self.args.cell) > _lib.LOCATOR_MAX_RATIO:
+            raise ValueError(f"closest: max_distance / cell = {r / float(self.args.cell):.1f} is beyond the ring limit {_lib.LOCATOR_MAX_RATIO}: "
+                             "build the locator with a larger cell (`locator(cell=...)`, `closest(..., cell=...)`)")
+        N, stride = int(points.shape[0]), int(points.shape[1])
+        dev = points.device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            d2 = torch.empty((N,), dtype=torch.float32, device=dev)
+            tri = torch.empty((N,), dtype=torch.int32, device=dev)
+            point = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            bary = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            counts = torch.empty((_lib.CLOSEST_COUNT,), dtype=torch.int32, device=dev)
+            _lib.check(lib.dif_mesh_closest(ctypes.byref(self.args), self.n_triangles, _lib.ptr(self.workspace), int(self.workspace.numel()), _lib.ptr(points), N,
+                                            stride, r, _lib.ptr(d2), _lib.ptr(tri), _lib.ptr(point), _lib.ptr(bary), _lib.ptr(counts), _lib.stream_ptr()),
+                       "dif_mesh_closest")
+            c = counts.cpu().tolist()
+        if c[_lib.CLOSEST_STATUS] != 0:
+            raise RuntimeError(f"libdifusion: dif_mesh_closest reported status {c[_lib.CLOSEST_STATUS]} (the locator was not built)")
+        return MeshClosest(d2, tri, point, bary, dict(zip(CLOSEST_COUNT_NAMES, c)))
+
+
+def locator_args(cell: float, pair_capacity: int, max_cells: Optional[int] = None) -> _lib.DifLocatorArgs:
+    a = _lib.DifLocatorArgs()
+    a.cell = float(cell)
+    a.max_cells = 0 if max_cells is None else int(max_cells)
+    a.pair_capacity = int(pair_capacity)
+    if not (a.cell > 0.0 and np.isfinite(a.cell)):
+        raise ValueError(f"locator: cell must be positive and finite (as float32); got {cell}")
+    if a.max_cells > 2 ** 20:
+        raise ValueError(f"locator: max_cells must not pass 2^20; got {max_cells}")
+    return a
+
+
+def locator(vertices: torch.Tensor, triangles: torch.Tensor, cell: Optional[float] = None, pair_capacity: Optional[int] = None,
+            max_cells: Optional[int] = None) -> MeshLocator:
+    """The flat operator: vertices (V,3) f32 and triangles (K,3) i32 on the GPU -> `MeshLocator` (`dif_mesh_locator_build`, include/difusion.h has
+    the contract).  `cell`: the edge of the grid's cubes, default `default_locator_cell` — no answer depends on it.  `pair_capacity`: room for
+    the (triangle, cell) pairs, default 8 K; when the mesh needs more the build reports how many and is repeated ONCE with that number (the
+    grow-and-retry of `extract_mesh_arrays`).  `max_cells`: a triangle whose box covers more cells goes to the large list that every query walks
+    (default 64; negative: every triangle, the all-pairs search).  One synchronisation per build (the counts), one more for the default cell."""
+    K = _check_triangles(triangles, "locator")
+    _lib.require_cuda(vertices)
+    V = int(vertices.shape[0])
+    if vertices.dtype != torch.float32 or tuple(vertices.shape) != (V, 3):
+        raise RuntimeError(f"locator: vertices must be (V,3) float32; got {tuple(vertices.shape)} {vertices.dtype}")
+    if vertices.device != triangles.device:
+        raise RuntimeError(f"locator: vertices live on {vertices.device}, triangles on {triangles.device}")
+    if pair_capacity is not None and int(pair_capacity) < 1:
+        raise ValueError(f"locator: pair_capacity must be at least 1; got {pair_capacity}")
+    if cell is None:
+        cell = default_locator_cell(vertices, triangles)
+    capacity = max(1024, 8 * K) if pair_capacity is None else int(pair_capacity)
+    dev = triangles.device
+    lib = _lib.load()
+    for attempt in range(2):
+        args = locator_args(cell, capacity, max_cells)
+        ws_bytes = int(lib.dif_mesh_locator_workspace_bytes(V, K, capacity))
+        if ws_bytes < 0:
+            raise RuntimeError(f"libdifusion: dif_mesh_locator_build cannot index {V} vertices, {K} triangles, {capacity} pairs (V and 3 K must stay "
+                               "below 2^31, the pairs below 2^28)")
+        with torch.cuda.device(dev):
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            counts = torch.empty((_lib.LOCATOR_COUNT,), dtype=torch.int32, device=dev)
+            _lib.check(lib.dif_mesh_locator_build(_lib.ptr(vertices), _lib.ptr(triangles), V, K, ctypes.byref(args), _lib.ptr(ws), ws_bytes, _lib.ptr(counts),
+                                                  _lib.stream_ptr()), "dif_mesh_locator_build")
+            c = counts.cpu().tolist()
+        if not (c[_lib.LOCATOR_STATUS] & _lib.MESH_STATUS_PAIR_OVERFLOW):
+            break
+        capacity = c[_lib.LOCATOR_PAIRS]                                          # the exact number; one retry
+    status = c[_lib.LOCATOR_STATUS]
+    if status & ~_lib.MESH_STATUS_BAD_INDEX:
+        raise RuntimeError(f"libdifusion: dif_mesh_locator_build reported status {status} ({c[_lib.LOCATOR_PAIRS]} pairs needed, room for {capacity})")
+    out = dict(zip(LOCATOR_COUNT_NAMES, c), cell=float(args.cell), max_cells=int(args.max_cells) if args.max_cells else _lib.LOCATOR_MAX_CELLS)
+    return MeshLocator(ws, args, K, out)
+
+
+def interpolate(triangles: torch.Tensor, closest_triangle: torch.Tensor, barycentric: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """The flat operator behind `IndexedMesh.interpolate`: plain torch indexing on the device, float32, (b0 x0 + b1 x1) + b2 x2."""
+    found = closest_triangle >= 0
+    corners = triangles.long()[closest_triangle.long().clamp(min=0)]                # (N,3)
+    x = values[corners]                                                           # (N,3) or (N,3,C)
+    b = barycentric if values.dim() == 1 else barycentric[:, :, None]
+    out = (b[:, 0] * x[:, 0] + b[:, 1] * x[:, 1]) + b[:, 2] * x[:, 2]
+    nan = torch.full_like(out, float("nan"))
+    return torch.where(found if values.dim() == 1 else found[:, None], out, nan)

@@ -511,6 +511,53 @@ int dif_mesh_simplify(const float* vertices, const float* vertex_std, const int3
                       float* out_vertices, float* out_normals, float* out_vertex_std, int32_t* out_triangles, int64_t* out_triangle_id,
                       uint64_t* out_colour_accum, int32_t* vertex_cluster, int32_t* counts, void* stream);
 
+/* Closest point on an indexed mesh for a cloud of query points (no reference counterpart; DESIGN.md "Closest point on an indexed mesh").
+ * dif_mesh_locator_build indexes the mesh once into `workspace`; dif_mesh_closest answers any number of query clouds from it (the mesh arrays
+ * are not read again: the workspace holds a copy of every usable triangle).  The distance is UNSIGNED.
+ * USABLE triangles.  A triangle is left out, and falls into exactly one class, tested in this order: an index outside [0, V) (BAD_INDEX, status bit
+ * DIF_MESH_STATUS_BAD_INDEX, never dereferenced); SKIPPED: a coordinate that is not finite or reaches 2^60 in magnitude, or the triangle's box
+ * leaves the key range of the grid (below); DEGENERATE: all three components of the float32 cross product of b - a and c - a (each multiply and
+ * subtract rounded once) are exactly zero — repeated indices included.
+ * d2 OF A PAIR (query p, usable triangle a b c), float32, every operation rounded once, dot(u, v) = (ux vx + uy vy) + uz vz:
+ *   ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c;  d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp),
+ *   d5 = dot(ab, cp), d6 = dot(ac, cp);  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e43 = d4 - d3, e56 = d5 - d6.
+ *   Region, first match: p == a, p == b, p == c (all three coordinates equal); d1 <= 0 and d2 <= 0: A; d3 >= 0 and d4 <= d3: B; d6 >= 0 and
+ *   d5 <= d6: C; vc <= 0, d1 >= 0, d3 <= 0: AB; vb <= 0, d2 >= 0, d6 <= 0: AC; va <= 0, e43 >= 0, e56 >= 0: BC; else the interior.
+ *   ratio(x, y) = fmin(fmax(y > 0 ? x / y : 0, 0), 1).  Closest point x and barycentrics (weights of a, b, c):
+ *     A, B, C: that vertex, bit for bit; (1,0,0), (0,1,0), (0,0,1).          AB: t = ratio(d1, d1 - d3), x = a + t ab, (1 - t, t, 0).
+ *     AC: t = ratio(d2, d2 - d6), x = a + t ac, (1 - t, 0, t).                BC: t = ratio(e43, e43 + e56), x = b + t bc, (0, 1 - t, t).
+ *     interior: den = (va + vb) + vc, v = ratio(vb, den), w = fmin(ratio(vc, den), 1 - v), x = a + (v ab + w ac), ((1 - v) - w, v, w).
+ *   d2 = (ex ex + ey ey) + ez ez with e = x - p.  A vertex of the mesh queried against the mesh therefore gives d2 = 0 exactly.
+ * ANSWER of a query: the usable triangle with the smallest (float bits of d2, triangle index) among those with d2 <= max_distance^2 (the
+ * float32 square: a pair exactly at max_distance is INSIDE).  It equals the all-pairs minimum for every cell size: the grid only decides the time.
+ *   out_d2 (N) f32, out_triangle (N) i32, out_point (N,3) f32, out_barycentric (N,3) f32.  No such triangle: inf, -1, NaN, NaN (FAR).  A query
+ *   that is not finite, reaches 2^60, or whose cell leaves the key range: the same outputs (BAD_POINT).  points: N rows of `stride` >= 3 floats.
+ * GRID: cubic cells of edge `cell`, cell coordinate floor(fl(x * fl(1 / cell))), |cell coordinate| < 2^20 - 64 (the key range), hashed: no bounding
+ * box.  A usable triangle is registered in every cell that its vertex box, widened per side by fl(2^-20 m) (m = its largest |coordinate|),
+ * overlaps; one whose box covers more than `max_cells` cells (0: DIF_LOCATOR_MAX_CELLS; negative: every triangle) goes to the LARGE list, which
+ * every query tests directly.  The (triangle, cell) pairs are not a function of K: the caller gives `pair_capacity`, counts[DIF_LOCATOR_PAIRS]
+ * reports the pairs NEEDED (saturating at INT32_MAX), and when they do not fit the status gets DIF_MESH_STATUS_PAIR_OVERFLOW, nothing is
+ * registered and dif_mesh_closest on that workspace answers FAR for every query and repeats the bit in its own status.  Build again with the
+ * number reported.
+ * counts (device, cleared by the call): int32[DIF_LOCATOR_COUNT] of the build — INDEXED + LARGE + DEGENERATE + SKIPPED + BAD_INDEX = K; CELLS = the
+ * distinct cells — and int32[DIF_CLOSEST_COUNT] of a query: FOUND + FAR + BAD_POINT = N.
+ * DIF_EINVAL: cell or max_distance not positive and finite, max_distance / cell above DIF_LOCATOR_MAX_RATIO (the ring encoding), max_cells above
+ * 2^20, V >= 2^31, 3 K >= 2^31, pair_capacity < 1 or >= 2^28 (the workspace size is then -1), stride < 3, a NULL args or counts, a NULL array that
+ * V, K or N says is not empty, a workspace that is NULL, not aligned to 16 bytes, or smaller than dif_mesh_locator_workspace_bytes.  K = 0, V = 0
+ * and N = 0 are valid.  dif_mesh_closest must be given the K and the args of the build. */
+typedef struct { float cell; int32_t max_cells; int64_t pair_capacity; } dif_locator_args_t;
+enum { DIF_MESH_STATUS_PAIR_OVERFLOW = 8 };
+enum { DIF_LOCATOR_MAX_CELLS = 64, DIF_LOCATOR_MAX_RATIO = 60 };
+enum { DIF_LOCATOR_INDEXED = 0, DIF_LOCATOR_LARGE = 1, DIF_LOCATOR_DEGENERATE = 2, DIF_LOCATOR_SKIPPED = 3, DIF_LOCATOR_BAD_INDEX = 4,
+       DIF_LOCATOR_PAIRS = 5, DIF_LOCATOR_CELLS = 6, DIF_LOCATOR_STATUS = 7, DIF_LOCATOR_COUNT = 8 };
+enum { DIF_CLOSEST_FOUND = 0, DIF_CLOSEST_FAR = 1, DIF_CLOSEST_BAD_POINT = 2, DIF_CLOSEST_STATUS = 3, DIF_CLOSEST_COUNT = 4 };
+int64_t dif_mesh_locator_workspace_bytes(int64_t V, int64_t K, int64_t pair_capacity);
+int dif_mesh_locator_build(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, const dif_locator_args_t* args, void* workspace,
+                           int64_t workspace_bytes, int32_t* counts, void* stream);
+int dif_mesh_closest(const dif_locator_args_t* args, int64_t K, const void* workspace, int64_t workspace_bytes, const float* points, int64_t N,
+                     int32_t stride, float max_distance, float* out_d2, int32_t* out_triangle, float* out_point, float* out_barycentric,
+                     int32_t* counts, void* stream);
+
 /* Depth, normal, std and triangle-index images of an indexed mesh seen from a pinhole camera (DESIGN.md "Rendering an indexed mesh").
  * Pixel (u, v) is column and row, its centre sits at integer coordinates, x = (u - cx) / fx * z (dif_unproject's convention).
  * Camera point = world_to_cam (row-major 3x4, float32) applied as ((r0 x + r1 y) + r2 z) + t.  A vertex is valid when that point is finite,
