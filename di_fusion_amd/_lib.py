@@ -140,6 +140,8 @@ LOCATOR_MAX_CELLS, LOCATOR_MAX_RATIO = 64, 60                                   
 (LOCATOR_INDEXED, LOCATOR_LARGE, LOCATOR_DEGENERATE, LOCATOR_SKIPPED, LOCATOR_BAD_INDEX, LOCATOR_PAIRS, LOCATOR_CELLS, LOCATOR_STATUS) = range(8)   # DIF_LOCATOR_*
 LOCATOR_COUNT = 8
 CLOSEST_FOUND, CLOSEST_FAR, CLOSEST_BAD_POINT, CLOSEST_STATUS, CLOSEST_COUNT = 0, 1, 2, 3, 4           # DIF_CLOSEST_*
+SAMPLER_WEIGHTED, SAMPLER_WEIGHTLESS, SAMPLER_SKIPPED, SAMPLER_BAD_INDEX, SAMPLER_EXPONENT, SAMPLER_STATUS, SAMPLER_COUNT = 0, 1, 2, 3, 4, 5, 8   # DIF_SAMPLER_*
+SAMPLE_SAMPLES, SAMPLE_STATUS, SAMPLE_COUNT = 0, 1, 2                                                  # DIF_SAMPLE_*
 RASTER_PIXELS_HIT, RASTER_DRAWN, RASTER_CLIPPED, RASTER_DEGENERATE, RASTER_CULLED, RASTER_OFFSCREEN, RASTER_LARGE, RASTER_STATUS, RASTER_COUNT = range(9)   # DIF_RASTER_*
 RASTER_THREAD_PIXELS = 64                                                                              # DIF_RASTER_THREAD_PIXELS
 COLOUR_USED, COLOUR_NO_HIT, COLOUR_BAD_COLOUR, COLOUR_DEPTH, COLOUR_EDGE, COLOUR_GRAZING, COLOUR_STATUS, COLOUR_COUNT = 0, 1, 2, 3, 4, 5, 6, 8   # DIF_COLOUR_*
@@ -201,6 +203,10 @@ SIGNATURES = {
     "dif_mesh_locator_build": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, POINTER(DifLocatorArgs), c_void_p, c_int64, c_void_p, c_void_p]),
     "dif_mesh_closest": (c_int32, [POINTER(DifLocatorArgs), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_sampler_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dif_mesh_sampler_build": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "dif_mesh_sample": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "dif_mesh_render_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
     "dif_mesh_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DifRasterArgs), c_void_p, c_int64, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),

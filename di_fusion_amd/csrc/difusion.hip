@@ -152,6 +152,7 @@ inline int cu_blocks(int64_t items, int per_block) { return grid_for(items, per_
 #include "kernels_components.hip.h"
 #include "kernels_simplify.hip.h"
 #include "kernels_closest.hip.h"
+#include "kernels_sample.hip.h"
 #include "kernels_raster.hip.h"
 #include "kernels_colour.hip.h"
 #include "kernels_optimize.hip.h"
@@ -2093,6 +2094,71 @@ int dif_mesh_closest(const dif_locator_args_t* args, int64_t K, const void* work
     const LocQueryOut out{out_d2, out_triangle, out_point, out_barycentric};
     hipLaunchKernelGGL(k_loc_query, dim3(mesh_blocks(N)), dim3(DIF_BLOCK), 0, s, ws.L, (int)K, points, (int)N, (int)stride, max_distance * max_distance, max_ring, out,
                        counts);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+// ---- sampling an indexed mesh -----------------------------------------------------------------------------------------
+extern "C++" {
+struct SamplerWs { Sampler S; int64_t total_bytes; };
+
+static int carve_sampler(int64_t V, int64_t K, void* base, SamplerWs& ws) {
+    if (!mesh_sizes_ok(V, K)) return DIF_EINVAL;
+    const size_t nk = (size_t)(K > 0 ? K : 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    const size_t o_head = take(sizeof(SamplerHead)), o_norm = take(nk * 8), o_prefix = take(nk * 8), o_tot = take(1024 * 8);
+    ws.total_bytes = (int64_t)off;
+    if (base) {
+        char* b = (char*)base;
+        ws.S.head = (SamplerHead*)(b + o_head);
+        ws.S.norm = (double*)(b + o_norm);
+        ws.S.prefix = (unsigned long long*)(b + o_prefix);
+        ws.S.block_tot = (unsigned long long*)(b + o_tot);
+    }
+    return DIF_OK;
+}
+}  // extern "C++"
+
+int64_t dif_mesh_sampler_workspace_bytes(int64_t V, int64_t K) {
+    SamplerWs ws;
+    if (carve_sampler(V, K, nullptr, ws) != DIF_OK) return -1;
+    return ws.total_bytes;
+}
+
+int dif_mesh_sampler_build(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, void* workspace, int64_t workspace_bytes,
+                           int32_t* counts, uint64_t* total, void* stream) {
+    if (!counts || !total) return DIF_EINVAL;
+    if ((V > 0 && !vertices) || (K > 0 && !triangles)) return DIF_EINVAL;
+    SamplerWs ws;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || carve_sampler(V, K, workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(ws.S.head, 0, sizeof(SamplerHead), s) != hipSuccess) return DIF_ELAUNCH;
+    const int nb = scan_blocks(K);
+    if (K > 0) {
+        // (V = 0: every index is out of range — k_smp_weigh reports it and dereferences nothing)
+        hipLaunchKernelGGL(k_smp_weigh, dim3(mesh_blocks(K)), dim3(DIF_BLOCK), 0, s, ws.S, vertices, (const int*)triangles, (int)K, (int)V);
+        hipLaunchKernelGGL(k_smp_sum, dim3(nb), dim3(DIF_BLOCK), 0, s, ws.S, (int)K);
+        DIF_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_smp_scan, dim3(nb), dim3(DIF_BLOCK), 0, s, ws.S, (int)K, counts, (unsigned long long*)total);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
+
+int dif_mesh_sample(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, const void* workspace, int64_t workspace_bytes, int64_t N,
+                    uint64_t seed, float* out_point, int32_t* out_triangle, float* out_barycentric, int32_t* counts, void* stream) {
+    if (!counts || N < 0 || N >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    if ((V > 0 && !vertices) || (K > 0 && !triangles)) return DIF_EINVAL;
+    if (N > 0 && (!out_point || !out_triangle || !out_barycentric)) return DIF_EINVAL;
+    SamplerWs ws;
+    if (!workspace || ((uintptr_t)workspace & 15) != 0 || carve_sampler(V, K, (void*)workspace, ws) != DIF_OK || ws.total_bytes > workspace_bytes) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * DIF_SAMPLE_COUNT, s) != hipSuccess) return DIF_ELAUNCH;
+    const SampleOut out{out_point, out_triangle, out_barycentric};
+    // (N = 0: one workgroup, whose first thread writes the counts and nothing else)
+    hipLaunchKernelGGL(k_smp_sample, dim3(N > 0 ? mesh_blocks(N) : 1), dim3(DIF_BLOCK), 0, s, ws.S, vertices, (const int*)triangles, (int)K, (int)V, (int)N,
+                       (unsigned long long)seed, out, counts);
     DIF_CHECK_LAUNCH();
     return DIF_OK;
 }

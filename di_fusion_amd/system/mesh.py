@@ -6,7 +6,10 @@ components, an edge census and the selection of a sub-mesh (`dif_mesh_components
 DESIGN.md "Rendering an indexed mesh").  And its colour: RGB keyframes splatted onto the vertices through that rasteriser (`dif_mesh_colour_view`,
 `dif_mesh_colour_resolve`; DESIGN.md "Colouring an indexed mesh").  And a smaller one: vertex clustering on a grid (`dif_mesh_simplify`; DESIGN.md
 "Simplifying an indexed mesh").  And its distance to anything: the exact closest point on its surface for a cloud of points
-(`dif_mesh_locator_build`, `dif_mesh_closest`; DESIGN.md "Closest point on an indexed mesh").
+(`dif_mesh_locator_build`, `dif_mesh_closest`; DESIGN.md "Closest point on an indexed mesh").  And points ON it: samples drawn uniformly by
+area, a pure function of (mesh, N, seed) (`dif_mesh_sampler_build`, `dif_mesh_sample`; DESIGN.md "Sampling an indexed mesh"), and on those the
+two-sided comparison of two surfaces — accuracy, completeness, Chamfer distance, precision / recall / F-score (`IndexedMesh.compare`) — with
+`read_ply` to load the other one.
 """
 from __future__ import annotations
 
@@ -124,12 +127,50 @@ class IndexedMesh:
     def interpolate(self, closest: "MeshClosest", values: torch.Tensor) -> torch.Tensor:
         """A per-vertex attribute `values` (V,) or (V,C) f32 of THIS mesh at the closest points of `closest` (a result of this mesh's locator):
         (b0 x0 + b1 x1) + b2 x2 per row with the barycentrics and the triangle's three vertices in index order, in float32 — what carries std,
-        normals or colours from one mesh to the points (or the vertices) of another.  Rows without a closest point are NaN."""
+        normals or colours from one mesh to the points (or the vertices) of another.  Rows without a closest point are NaN.
+        A `MeshSamples` of this mesh (`sample`) has the same two fields: `interpolate(samples, self.normals)` is a normal per sample."""
         _lib.require_cuda(values, closest.triangle, closest.barycentric)
         V = int(self.vertices.shape[0])
         if values.dtype != torch.float32 or values.dim() not in (1, 2) or int(values.shape[0]) != V:
             raise RuntimeError(f"interpolate: values must be ({V},) or ({V},C) float32; got {tuple(values.shape)} {values.dtype}")
         return interpolate(self.triangles, closest.triangle, closest.barycentric, values)
+
+    def sampler(self) -> "MeshSampler":
+        """A `MeshSampler` over this mesh's surface (`sampler`): build once, draw with `.sample` as often as needed."""
+        return sampler(self.vertices, self.triangles)
+
+    def sample(self, n: int, seed: int = 0) -> "MeshSamples":
+        """`n` points drawn uniformly by area from this mesh's surface (`MeshSampler.sample`), a pure function of (mesh, n, seed).  The result has
+        the two fields `interpolate` reads, so `mesh.interpolate(mesh.sample(n), mesh.normals)` is a normal per sample: any mesh as an xyz +
+        normal cloud.  Builds a sampler for the one call: keep `self.sampler()` when there are several draws."""
+        return self.sampler().sample(n, seed)
+
+    def compare(self, other: "IndexedMesh", max_distance: float, n_samples: int = 100_000, seed: int = 0,
+                thresholds: Sequence[float] = (0.005, 0.01, 0.02), cell: Optional[float] = None) -> dict:
+        """The two-sided, AREA-SAMPLED comparison of two surfaces: `n_samples` points on this mesh (seed) against `other`'s surface — `accuracy` —
+        and `n_samples` points on `other` (seed + 1) against this one's — `completeness`.  Each direction is a dict of `mean`, `rms`, `median`,
+        `max` of the distance over the samples that found a point within `max_distance` (NaN when none did; the median is the lower middle, as
+        torch's), the counts `found` and `far`, and `within`: per threshold, how many samples lie at d <= tau (a far sample never does).  On top:
+        `chamfer` = the mean of the two means, `thresholds`, and per threshold `precision` = within of accuracy / samples drawn, `recall` = the
+        same of completeness, `fscore` = 2 P R / (P + R), or 0 when P + R = 0 (a surface without area draws no samples: 0).  d = sqrt(d2) in
+        float64 from the closest operator's float32 d2; the reductions run on the device in float64.  Unsigned.  `cell`: the cell of both
+        locators; default: `distance_to`'s rule for each.  Every threshold must be <= `max_distance` (ValueError)."""
+        taus = [float(t) for t in thresholds]
+        r = float(np.float32(max_distance))
+        for t in taus:
+            if not t <= r:
+                raise ValueError(f"compare: threshold {t} is beyond max_distance {r} (as float32): a sample beyond max_distance finds nothing")
+        n = int(n_samples)
+        seed = int(seed)
+        out = dict(thresholds=tuple(taus))
+        for name, a, b, s in (("accuracy", self, other, seed), ("completeness", other, self, seed + 1)):
+            pts = a.sample(n, s)
+            out[name] = _sampled_distance(pts.point, int(pts.counts["samples"]), b, max_distance, cell, taus)
+        out["chamfer"] = 0.5 * (out["accuracy"]["mean"] + out["completeness"]["mean"])
+        out["precision"] = [w / n if n else 0.0 for w in out["accuracy"]["within"]]
+        out["recall"] = [w / n if n else 0.0 for w in out["completeness"]["within"]]
+        out["fscore"] = [2.0 * p * q / (p + q) if p + q > 0 else 0.0 for p, q in zip(out["precision"], out["recall"])]
+        return out
 
     def render(self, pose, intrinsics, height: int, width: int, z_near: float = 0.05, cull_backfaces: bool = False) -> "MeshRender":
         """Depth, normal, std and triangle-index images of this mesh from the camera-to-world `pose` (`render`)."""
@@ -793,3 +834,191 @@ def interpolate(triangles: torch.Tensor, closest_triangle: torch.Tensor, barycen
     out = (b[:, 0] * x[:, 0] + b[:, 1] * x[:, 1]) + b[:, 2] * x[:, 2]
     nan = torch.full_like(out, float("nan"))
     return torch.where(found if values.dim() == 1 else found[:, None], out, nan)
+
+
+def _sampled_distance(points: torch.Tensor, drawn: int, target: IndexedMesh, max_distance: float, cell: Optional[float], taus) -> dict:
+    """One direction of `IndexedMesh.compare`: `points` (the first `drawn` rows are samples) against `target`'s surface."""
+    nan = float("nan")
+    if drawn == 0:
+        return dict(mean=nan, rms=nan, median=nan, max=nan, found=0, far=0, within=[0] * len(taus))
+    if cell is None:
+        r = float(np.float32(max_distance))
+        cell = default_locator_cell(target.vertices, target.triangles)
+        if np.isfinite(r) and r > 0.0:
+            cell = max(cell, float(np.float32(r / (_lib.LOCATOR_MAX_RATIO - 1))))
+    c = target.locator(cell).closest(points, max_distance)
+    with torch.cuda.device(points.device):
+        d = torch.sqrt(c.d2[torch.isfinite(c.d2)].double())
+        within = [(d <= t).sum().double() for t in taus]
+        if d.numel() > 0:
+            stats = torch.stack([d.mean(), torch.sqrt((d * d).mean()), d.median(), d.max()] + within).cpu().tolist()
+        else:
+            stats = [nan] * 4 + [0.0] * len(taus)
+    return dict(mean=stats[0], rms=stats[1], median=stats[2], max=stats[3], found=c.counts["found"], far=c.counts["far"] + c.counts["bad_point"],
+                within=[int(w) for w in stats[4:]])
+
+
+# ---- sampling (DESIGN.md "Sampling an indexed mesh") -----------------------------------------------------------------------------------
+SAMPLER_COUNT_NAMES = ("weighted", "weightless", "skipped", "bad_index", "exponent", "status")
+SAMPLE_COUNT_NAMES = ("samples", "status")
+
+
+class MeshSamples:
+    """point (N,3) f32, triangle (N,) i32, barycentric (N,3) f32 (the weights of the triangle's three vertices in index order) — device tensors,
+    `.cpu()` for a host copy — in ascending triangle order, and `counts`: samples (N, or 0 when the mesh has no area: every row is then NaN / -1 /
+    NaN), status.  `triangle` and `barycentric` are what `IndexedMesh.interpolate` reads: `mesh.interpolate(samples, mesh.normals)`."""
+
+    def __init__(self, point, triangle, barycentric, counts: dict):
+        self.point = point
+        self.triangle = triangle
+        self.barycentric = barycentric
+        self.counts = dict(counts)
+
+    def cpu(self) -> "MeshSamples":
+        return MeshSamples(self.point.cpu(), self.triangle.cpu(), self.barycentric.cpu(), self.counts)
+
+
+class MeshSampler:
+    """The weights of one mesh's triangles (`sampler`): `workspace` (device bytes: the prefix sums), the mesh arrays it was built from (read again
+    by every draw), `counts` — triangles weighted / weightless (degenerate, or 2^32 times smaller than the largest: they get no samples) / skipped
+    (not finite, or a coordinate of 2^60) / bad_index, the exponent e of the largest doubled area, status (may hold `_lib.MESH_STATUS_BAD_INDEX`)
+    — `total` = T, the sum of the integer weights, and `area` = 0.5 T 2^(e - 32): the float64 area of the float32 vertices, short by less than
+    2^(e - 33) per triangle."""
+
+    def __init__(self, workspace: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, counts: dict, total: int):
+        self.workspace = workspace
+        self.vertices = vertices
+        self.triangles = triangles
+        self.counts = dict(counts)
+        self.total = int(total)
+        self.area = float(np.ldexp(float(self.total), int(self.counts["exponent"]) - 33))
+
+    def sample(self, n: int, seed: int = 0) -> MeshSamples:
+        """`n` stratified samples (0 <= n < 2^31) -> `MeshSamples`: sample j lies in the j-th of n equal parts of the summed weights, so a triangle
+        of weight w gets within 2 of n w / T samples, whatever the seed; the seed (any integer, taken modulo 2^64) moves the samples inside their
+        strata and on their triangles.  Stratified jitter, not blue noise.  One synchronisation (the counts)."""
+        n = int(n)
+        if n < 0 or n >= 2 ** 31:
+            raise ValueError(f"sample: n must be in [0, 2^31); got {n}")
+        V, K = int(self.vertices.shape[0]), int(self.triangles.shape[0])
+        dev = self.workspace.device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            tri = torch.empty((n,), dtype=torch.int32, device=dev)
+            bary = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            counts = torch.empty((_lib.SAMPLE_COUNT,), dtype=torch.int32, device=dev)
+            _lib.check(lib.dif_mesh_sample(_lib.ptr(self.vertices), _lib.ptr(self.triangles), V, K, _lib.ptr(self.workspace), int(self.workspace.numel()), n,
+                                           int(seed) & (2 ** 64 - 1), _lib.ptr(point), _lib.ptr(tri), _lib.ptr(bary), _lib.ptr(counts), _lib.stream_ptr()),
+                       "dif_mesh_sample")
+            c = counts.cpu().tolist()
+        if c[_lib.SAMPLE_STATUS] & ~_lib.MESH_STATUS_BAD_INDEX or c[_lib.SAMPLE_STATUS] != self.counts["status"]:
+            raise RuntimeError(f"libdifusion: dif_mesh_sample reported status {c[_lib.SAMPLE_STATUS]} (the sampler was not built for this mesh)")
+        return MeshSamples(point, tri, bary, dict(zip(SAMPLE_COUNT_NAMES, c)))
+
+
+def sampler(vertices: torch.Tensor, triangles: torch.Tensor) -> MeshSampler:
+    """The flat operator: vertices (V,3) f32 and triangles (K,3) i32 on the GPU -> `MeshSampler` (`dif_mesh_sampler_build`, include/difusion.h has
+    the contract).  The weight of a triangle is an INTEGER — its doubled area in double, scaled by a power of two so that the largest lies in
+    [2^31, 2^32), floored — so the prefix sums are exact and the same on every run.  One synchronisation (the counts and T)."""
+    K = _check_triangles(triangles, "sampler")
+    _lib.require_cuda(vertices)
+    V = int(vertices.shape[0])
+    if vertices.dtype != torch.float32 or tuple(vertices.shape) != (V, 3):
+        raise RuntimeError(f"sampler: vertices must be (V,3) float32; got {tuple(vertices.shape)} {vertices.dtype}")
+    if vertices.device != triangles.device:
+        raise RuntimeError(f"sampler: vertices live on {vertices.device}, triangles on {triangles.device}")
+    dev = triangles.device
+    lib = _lib.load()
+    ws_bytes = int(lib.dif_mesh_sampler_workspace_bytes(V, K))
+    if ws_bytes < 0:
+        raise RuntimeError(f"libdifusion: dif_mesh_sampler_build cannot index {V} vertices, {K} triangles (V and 3 K must stay below 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        back = torch.empty((_lib.SAMPLER_COUNT // 2 + 1,), dtype=torch.int64, device=dev)      # the counts (int32) and T behind them: one read-back
+        _lib.check(lib.dif_mesh_sampler_build(_lib.ptr(vertices), _lib.ptr(triangles), V, K, _lib.ptr(ws), ws_bytes, _lib.ptr(back),
+                                              ctypes.c_void_p(back.data_ptr() + 4 * _lib.SAMPLER_COUNT), _lib.stream_ptr()), "dif_mesh_sampler_build")
+        host = back.cpu()
+    c = host[:_lib.SAMPLER_COUNT // 2].view(torch.int32).tolist()
+    total = int(host[-1].item()) & (2 ** 64 - 1)
+    return MeshSampler(ws, vertices, triangles, dict(zip(SAMPLER_COUNT_NAMES, c)), total)
+
+
+# ---- reading a PLY ---------------------------------------------------------------------------------------------------------------------
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+                "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def read_ply(path, device="cuda") -> IndexedMesh:
+    """A binary little-endian PLY as an `IndexedMesh` on `device` (numpy alone): the other mesh of a comparison, or what `write_ply` wrote, array
+    for array and bit for bit.  Vertex properties: scalars of any PLY type in any order; `x y z` are required and, like `nx ny nz` and
+    `quality` (-> vertex_std), taken as float32 — bit for bit when the file holds `float`; `red green blue` as uint8 when they are `uchar` (with
+    color_weight 1).  Without them normals and std are zero and colours None.  Faces: `property list uchar int|uint vertex_indices` (or
+    `vertex_index`), triangles only.  `triangle_flatten_id` is -1.  Elements after the faces are not read.  Anything else — ASCII, big-endian,
+    a list property on a vertex, another face layout, a face that is not a triangle, a truncated file — raises ValueError and names what it found."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"read_ply: {path}: not a PLY file (no 'ply' magic or no end_header)")
+    lines = [ln.strip() for ln in data[:end].decode("ascii", errors="replace").splitlines()]
+    body = end + len(b"end_header\n")
+    fmt = [ln.split() for ln in lines if ln.startswith("format")]
+    if not fmt or fmt[0][1:] != ["binary_little_endian", "1.0"]:
+        raise ValueError(f"read_ply: {path}: only 'format binary_little_endian 1.0' is read; found {' '.join(fmt[0]) if fmt else 'no format line'!r}")
+    elements = []                                                                 # [name, count, [property tokens]]
+    for ln in lines:
+        tok = ln.split()
+        if tok[:1] == ["element"]:
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[:1] == ["property"]:
+            if not elements:
+                raise ValueError(f"read_ply: {path}: a property before any element: {ln!r}")
+            elements[-1][2].append(tok[1:])
+    names = [e[0] for e in elements]
+    if names[:2] != ["vertex", "face"]:
+        raise ValueError(f"read_ply: {path}: the first two elements must be vertex and face; found {names}")
+    (_, V, vprops), (_, K, fprops) = elements[:2]
+    fields = []
+    for p in vprops:
+        if p[0] == "list" or p[0] not in _PLY_SCALARS or len(p) != 2:
+            raise ValueError(f"read_ply: {path}: vertex properties must be scalars; found 'property {' '.join(p)}'")
+        fields.append((p[1], _PLY_SCALARS[p[0]]))
+    have = [n for n, _ in fields]
+    if len(set(have)) != len(have) or not all(k in have for k in "xyz"):
+        raise ValueError(f"read_ply: {path}: the vertex needs x, y and z, each once; found {have}")
+    if len(fprops) != 1 or fprops[0][0] != "list" or len(fprops[0]) != 4 or fprops[0][1] not in ("uchar", "uint8") or \
+            fprops[0][2] not in ("int", "int32", "uint", "uint32") or fprops[0][3] not in ("vertex_indices", "vertex_index"):
+        raise ValueError(f"read_ply: {path}: faces must be 'property list uchar int|uint vertex_indices'; found {[' '.join(p) for p in fprops]}")
+    vdt = np.dtype(fields)
+    fdt = np.dtype([("n", "u1"), ("v", _PLY_SCALARS[fprops[0][2]], (3,))])
+    need_v = V * vdt.itemsize
+    if len(data) - body < need_v:
+        raise ValueError(f"read_ply: {path}: truncated: {V} vertices of {vdt.itemsize} bytes need {need_v} bytes, the file has {len(data) - body} after its header")
+    vert = np.frombuffer(data, dtype=vdt, count=V, offset=body)
+    # (a face that is not a triangle shifts every later one: look at the counts one face at a time, as far as the file goes)
+    avail = (len(data) - body - need_v) // fdt.itemsize
+    face = np.frombuffer(data, dtype=fdt, count=min(K, avail), offset=body + need_v)
+    wrong = np.nonzero(face["n"] != 3)[0]
+    if wrong.size:
+        raise ValueError(f"read_ply: {path}: face {int(wrong[0])} has {int(face['n'][wrong[0]])} vertices; only triangles are read")
+    if avail < K:
+        raise ValueError(f"read_ply: {path}: truncated: {K} faces of {fdt.itemsize} bytes need {K * fdt.itemsize} bytes, the file has {len(data) - body - need_v} after "
+                         "its vertices")
+    tri = face["v"]
+    if tri.dtype.kind == "u" and K and int(tri.max()) >= 2 ** 31:
+        raise ValueError(f"read_ply: {path}: a vertex index of {int(tri.max())} does not fit int32")
+
+    def column(keys, default):
+        if all(k in have for k in keys):
+            return np.ascontiguousarray(np.stack([vert[k].astype(np.float32) for k in keys], axis=1))
+        return np.full((V, len(keys)), default, dtype=np.float32)
+
+    rgb = ("red", "green", "blue")
+    coloured = all(k in have and vdt[k] == np.uint8 for k in rgb)
+    dev = torch.device(device)
+    put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return IndexedMesh(put(column("xyz", 0.0)), put(column(("nx", "ny", "nz"), 0.0)), put(column(("quality",), 0.0)[:, 0]), put(tri.astype(np.int32)),
+                       put(np.full((K,), -1, dtype=np.int64)), dict(vertices=V, triangles=K, status=0),
+                       put(np.stack([vert[k] for k in rgb], axis=1)) if coloured else None,
+                       put(np.ones((V,), dtype=np.float32)) if coloured else None)

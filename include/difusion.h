@@ -558,6 +558,38 @@ int dif_mesh_closest(const dif_locator_args_t* args, int64_t K, const void* work
                      int32_t stride, float max_distance, float* out_d2, int32_t* out_triangle, float* out_point, float* out_barycentric,
                      int32_t* counts, void* stream);
 
+/* Points drawn uniformly by area from the surface of an indexed mesh (no reference counterpart; DESIGN.md "Sampling an indexed mesh").
+ * dif_mesh_sampler_build weighs the triangles once into `workspace`; dif_mesh_sample draws any number of sample sets from it and the mesh arrays.
+ * Deterministic, independent of the schedule: sample j is a pure function of (mesh, N, seed).  Every float operation below is rounded once, in the
+ * order written (no contraction).
+ * CLASS of a triangle, exactly one, tested in this order: BAD_INDEX, an index outside [0, V) (status bit DIF_MESH_STATUS_BAD_INDEX, never
+ * dereferenced); SKIPPED, a coordinate that is not finite or |x| >= 2^60; WEIGHTLESS, integer weight 0; WEIGHTED.
+ * WEIGHT (the last two classes): the nine float32 coordinates as double; e1 = p1 - p0, e2 = p2 - p0; c = e1 x e2, cx = e1y e2z - e1z e2y, cy = e1z e2x
+ * - e1x e2z, cz = e1x e2y - e1y e2x; s = (cx cx + cy cy) + cz cz; n = sqrt(s), correctly rounded.  m = the largest n of the mesh; e = the binary
+ * exponent with m 2^-e in [0.5, 1) (frexp; 0 when m = 0); w = floor(ldexp(n, 32 - e)): an exact scaling, the largest weight lies in [2^31, 2^32).
+ * A triangle of the first two classes has weight 0.  P = the inclusive prefix sums of w in index order and T their total, uint64 (T < 2^63): exact in
+ * any order.  m = 0 or K = 0: T = 0.  The doubled area of the mesh is about T 2^(e - 32), short by less than 2^(e - 32) per triangle.
+ * RANDOM BITS, uint64 with wrap-around: mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; z ^ z >> 31 (splitmix64).  base = mix(seed), r0(j) = mix(base ^ mix(2 j)), r1(j) = mix(base ^ mix(2 j + 1)).
+ * SAMPLE j of N (stratified): q = T div N, r = T mod N, b(j) = q j + (r j) div N; stratum j is [b(j), b(j + 1)), at least 1 wide since T >= 2^31 > N;
+ * t = b(j) + r0(j) mod (b(j + 1) - b(j)); the triangle is the first i with P[i] > t — never one without weight, and ascending in j.
+ * u = r1 >> 40, v = (r1 >> 16) & 0xFFFFFF; if u + v > 2^24 both are replaced by 2^24 - u, 2^24 - v; barycentric = ((2^24 - u - v) / 2^24, u / 2^24,
+ * v / 2^24), exact in float32, the weights of the triangle's vertices in index order; point = (b0 p0 + b1 p1) + b2 p2 per axis in float32.
+ *   out_point (N,3) f32, out_triangle (N) i32, out_barycentric (N,3) f32.  T = 0: every row is NaN, -1, NaN and SAMPLES is 0.
+ * counts (device, written by the call): int32[DIF_SAMPLER_COUNT] of the build — WEIGHTED + WEIGHTLESS + SKIPPED + BAD_INDEX = K, EXPONENT = e — with T
+ * in *total; int32[DIF_SAMPLE_COUNT] of a draw: SAMPLES (N, or 0 when T = 0) and STATUS (the build's).
+ * DIF_EINVAL: V >= 2^31 or 3 K >= 2^31 (the workspace size is then -1), N < 0 or N >= 2^31, a NULL counts or total, a NULL array that V, K or N says
+ * is not empty, a workspace that is NULL, not aligned to 16 bytes, or smaller than dif_mesh_sampler_workspace_bytes.  K = 0, V = 0 and N = 0 are
+ * valid.  dif_mesh_sample must be given the mesh, V and K of the build. */
+enum { DIF_SAMPLER_WEIGHTED = 0, DIF_SAMPLER_WEIGHTLESS = 1, DIF_SAMPLER_SKIPPED = 2, DIF_SAMPLER_BAD_INDEX = 3, DIF_SAMPLER_EXPONENT = 4,
+       DIF_SAMPLER_STATUS = 5, DIF_SAMPLER_COUNT = 8 };
+enum { DIF_SAMPLE_SAMPLES = 0, DIF_SAMPLE_STATUS = 1, DIF_SAMPLE_COUNT = 2 };
+int64_t dif_mesh_sampler_workspace_bytes(int64_t V, int64_t K);
+int dif_mesh_sampler_build(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, void* workspace, int64_t workspace_bytes,
+                           int32_t* counts, uint64_t* total, void* stream);
+int dif_mesh_sample(const float* vertices, const int32_t* triangles, int64_t V, int64_t K, const void* workspace, int64_t workspace_bytes, int64_t N,
+                    uint64_t seed, float* out_point, int32_t* out_triangle, float* out_barycentric, int32_t* counts, void* stream);
+
 /* Depth, normal, std and triangle-index images of an indexed mesh seen from a pinhole camera (DESIGN.md "Rendering an indexed mesh").
  * Pixel (u, v) is column and row, its centre sits at integer coordinates, x = (u - cx) / fx * z (dif_unproject's convention).
  * Camera point = world_to_cam (row-major 3x4, float32) applied as ((r0 x + r1 y) + r2 z) + t.  A vertex is valid when that point is finite,
