@@ -127,6 +127,11 @@ class DifIntegrateViews(ctypes.Structure):
     _fields_ = [("pt_lin", c_void_p), ("pair_list", c_void_p), ("rec_next", c_void_p), ("rec", c_void_p)]
 
 
+class DifSdfHgViews(ctypes.Structure):
+    """include/difusion.h: dif_sdf_hg_views_t"""
+    _fields_ = [("sdf", c_void_p), ("std", c_void_p), ("grad", c_void_p), ("partial_offset", c_int64), ("ticket_offset", c_int64)]
+
+
 WELD_VERTICES, WELD_KEPT, WELD_DROPPED, WELD_UNKEYED, WELD_STATUS, WELD_COUNT = 0, 1, 2, 3, 4, 8       # DIF_WELD_*
 COMP_COMPONENTS, COMP_STATUS, COMP_COUNT = 0, 1, 4                                                     # DIF_COMP_*
 SELECT_VERTICES, SELECT_TRIANGLES, SELECT_STATUS, SELECT_COUNT = 0, 1, 2, 4                            # DIF_SELECT_*
@@ -240,6 +245,8 @@ SIGNATURES = {
     "dif_test_sdma_mode": (c_int32, [c_int32]),
     "dif_test_optimize_views": (c_int32, [c_int64, c_int64, c_void_p, POINTER(DifOptimizeViews)]),
     "dif_test_integrate_views": (c_int32, [c_int64, c_void_p, POINTER(DifIntegrateViews)]),
+    "dif_test_sdf_hg_views": (c_int32, [c_int64, c_void_p, POINTER(DifSdfHgViews)]),
+    "dif_test_sdf_hg_reduce": (c_int32, [c_void_p, c_int64, POINTER(DifSdfHg), c_void_p, c_int64, c_void_p, c_void_p]),
     "dif_sdma_info": (c_int32, [POINTER(c_int32)]),
     "dif_test_handoff": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "dif_queues_independent": (c_int32, [c_void_p, c_void_p]),

@@ -2359,6 +2359,23 @@ inline HgLayout hg_layout(int64_t N) {
     L.total = o;
     return L;
 }
+inline HgArgs hg_args_of(const dif_sdf_hg_t* args) {
+    HgArgs a;
+    for (int i = 0; i < 12; ++i) { a.Tc[i] = args->T_cur[i]; a.Td[i] = args->T_delta[i]; }
+    for (int i = 0; i < 9; ++i) a.Lt[i] = args->last_Rt[i];
+    a.robust = args->robust_kernel; a.k = args->robust_k; a.no_grad = args->no_grad ? 1 : 0;
+    return a;
+}
+// The reduction over the three per-point views of workspace `b` (grad is not read with no_grad): the one launch line of k_sdf_hg_reduce, shared by
+// dif_sdf_hg and the test hook dif_test_sdf_hg_reduce.  The ticket word is 0 when the kernel starts (the decoder's zero_word or a memset in front).
+int launch_sdf_hg_reduce(const float* obs_xyz, int64_t N, const HgArgs& a, char* b, const HgLayout& L, double* out, double* out_host, int64_t seq,
+                         hipStream_t s) {
+    const float* grad = a.no_grad ? nullptr : (const float*)(b + L.grad);
+    hipLaunchKernelGGL(k_sdf_hg_reduce, dim3(grid_for(N, 2 * DIF_BLOCK, HG_BLOCKS)), dim3(DIF_BLOCK), 0, s, (int)N, obs_xyz, (const float*)(b + L.sdf),
+                       (const float*)(b + L.std_), grad, a, (double*)(b + L.partial), (int*)(b + L.ticket), out, out_host, seq);
+    DIF_CHECK_LAUNCH();
+    return DIF_OK;
+}
 }  // namespace
 
 int64_t dif_sdf_hg_workspace_bytes(int64_t N) { return N < 0 ? 0 : hg_layout(N).total; }
@@ -2372,10 +2389,7 @@ int dif_sdf_hg(const dif_map_t* map, const dif_weights_t* w, const float* obs_xy
     hipStream_t s = (hipStream_t)stream_;
     char* b = (char*)ws;
     int* ticket = (int*)(b + L.ticket);
-    HgArgs a;
-    for (int i = 0; i < 12; ++i) { a.Tc[i] = args->T_cur[i]; a.Td[i] = args->T_delta[i]; }
-    for (int i = 0; i < 9; ++i) a.Lt[i] = args->last_Rt[i];
-    a.robust = args->robust_kernel; a.k = args->robust_k; a.no_grad = args->no_grad ? 1 : 0;
+    const HgArgs a = hg_args_of(args);
     float* grad = a.no_grad ? nullptr : (float*)(b + L.grad);
     if (N > 0) {
         // the decoder over ALL points of the posed cloud: pose, validity test (map.py:565-572) and latent look-up in its row fetch, std = 0 for the
@@ -2390,10 +2404,27 @@ int dif_sdf_hg(const dif_map_t* map, const dif_weights_t* w, const float* obs_xy
         const int rc = launch_decode(A, w, (N + 31) / 32, s);
         if (rc != DIF_OK) return rc;
     } else if (hipMemsetAsync(ticket, 0, sizeof(int), s) != hipSuccess) return DIF_ELAUNCH;
-    hipLaunchKernelGGL(k_sdf_hg_reduce, dim3(grid_for(N, 2 * DIF_BLOCK, HG_BLOCKS)), dim3(DIF_BLOCK), 0, s, (int)N, obs_xyz, (const float*)(b + L.sdf),
-                       (const float*)(b + L.std_), (const float*)grad, a, (double*)(b + L.partial), ticket, out, out_host, seq);
-    DIF_CHECK_LAUNCH();
+    return launch_sdf_hg_reduce(obs_xyz, N, a, b, L, out, out_host, seq, s);
+}
+
+int dif_test_sdf_hg_views(int64_t N, void* ws, dif_sdf_hg_views_t* out) {
+    if (N < 0 || N >= ((int64_t)1 << 31) || !ws || !out) return DIF_EINVAL;
+    const HgLayout L = hg_layout(N);
+    char* b = (char*)ws;
+    out->sdf = (float*)(b + L.sdf); out->std = (float*)(b + L.std_); out->grad = (float*)(b + L.grad);
+    out->partial_offset = L.partial; out->ticket_offset = L.ticket;
     return DIF_OK;
+}
+
+int dif_test_sdf_hg_reduce(const float* obs_xyz, int64_t N, const dif_sdf_hg_t* args, void* ws, int64_t ws_bytes, double* out, void* stream_) {
+    if (!args || !out || N < 0 || N >= ((int64_t)1 << 31)) return DIF_EINVAL;
+    if (args->robust_kernel < 0 || args->robust_kernel > 2) return DIF_EINVAL;
+    const HgLayout L = hg_layout(N);
+    if (!ws || ws_bytes < L.total || ((uintptr_t)ws & 255) != 0 || (N > 0 && !obs_xyz)) return DIF_EINVAL;
+    hipStream_t s = (hipStream_t)stream_;
+    char* b = (char*)ws;
+    if (hipMemsetAsync(b + L.ticket, 0, sizeof(int), s) != hipSuccess) return DIF_ELAUNCH;
+    return launch_sdf_hg_reduce(obs_xyz, N, hg_args_of(args), b, L, out, nullptr, 0, s);
 }
 
 // ---- the tracker's photometric term (photometric.cu, tracker.py:41-56, 131-172) ---------------------------------------------------------

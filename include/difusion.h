@@ -850,6 +850,18 @@ typedef struct dif_integrate_views {
     int32_t* pt_lin; uint32_t* pair_list; int32_t* rec_next; int64_t* rec;
 } dif_integrate_views_t;
 int dif_test_integrate_views(int64_t N, void* ws, dif_integrate_views_t* out);
+/* TEST HOOK: where dif_sdf_hg keeps its per-point rows inside its workspace `ws` for N points — sdf[N], std[N] (0: the decoder's mark of a point that
+ * is not valid; nothing else of such a row is written) and grad[N][3] (not written with no_grad), each view starting on a 256-byte boundary — and the
+ * byte offsets of the reduction's partial sums (HG_BLOCKS rows of 29 doubles) and of its ticket word.  Launches nothing. */
+typedef struct dif_sdf_hg_views {
+    float* sdf; float* std; float* grad;
+    int64_t partial_offset; int64_t ticket_offset;
+} dif_sdf_hg_views_t;
+int dif_test_sdf_hg_views(int64_t N, void* ws, dif_sdf_hg_views_t* out);
+/* TEST HOOK: the second launch of dif_sdf_hg alone, on whatever the three views of `ws` hold: the ticket word is set to 0 by a memset, then the
+ * reduction runs, launched by the same line as in dif_sdf_hg; no decoder, no map.  Arguments are validated as dif_sdf_hg validates them; only
+ * T_delta, last_Rt, the robust kernel and no_grad of `args` are read.  out (device, 44 doubles) as dif_sdf_hg. */
+int dif_test_sdf_hg_reduce(const float* obs_xyz, int64_t N, const dif_sdf_hg_t* args, void* ws, int64_t ws_bytes, double* out, void* stream);
 /* TEST HOOK: a litmus run of the fence-free hand-overs the product kernels use (write-through stores + s_waitcnt vmcnt(0) + word on the producer,
  * sc1 loads on the consumer; csrc/kernels_litmus.hip.h).  mode 0: `groups` workgroups meet `iters` times through a counter every one polls, each then
  * checks another workgroup's 29-double record (a launch-wide meeting: the pattern of profiles/r06_experiments.md 1); mode 1: the last arriver of a ticket checks all records
