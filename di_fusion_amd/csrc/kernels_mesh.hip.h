@@ -236,15 +236,18 @@ __global__ void __launch_bounds__(DIF_BLOCK) k_marching_cubes(McArgs a) {
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
                 voxel_offset = part;
-                // mesh-cache log: this voxel's previous batch dies, the voxel points at its new one (map.py:708-709)
+                // mesh-cache log: this voxel's previous batch dies, the voxel points at its new one (map.py:708-709) — if the cut by
+                // max_n_triangles / the log's capacity leaves it a triangle: the reference drops cached triangles only for ids that occur among
+                // the triangles it KEPT, so a voxel cut off whole keeps its old batch (include/difusion.h: max_triangles)
                 const int64_t slot = a.indexer[vb], log_n = a.log_counters[DIF_C_CACHE_KEPT];
                 const int old_n = a.tri_n[slot], old_s = a.tri_start[slot];
-                for (int j = lane; j < old_n; j += 64) a.tri_alive[old_s + j] = 0;
                 int64_t n_new = a.tri_count[k];
                 if (voxel_offset + n_new > a.new_limit) n_new = a.new_limit > voxel_offset ? a.new_limit - voxel_offset : 0;      // truncated by max_n_triangles
                 if (log_n + voxel_offset + n_new > a.max_triangles) n_new = a.max_triangles > log_n + voxel_offset ? a.max_triangles - (log_n + voxel_offset) : 0;
+                if (n_new > 0)
+                    for (int j = lane; j < old_n; j += 64) a.tri_alive[old_s + j] = 0;
                 __builtin_amdgcn_wave_barrier();             // every lane has read tri_n / tri_start
-                if (lane == 0) {
+                if (lane == 0 && n_new > 0) {
                     a.tri_start[slot] = (int)(log_n + voxel_offset);
                     a.tri_n[slot] = (int)n_new;
                     if (old_n) atomicAdd(a.log_counters + DIF_C_CACHE_DEAD, old_n);
@@ -416,10 +419,11 @@ __device__ __forceinline__ bool mc_load_voxel(const McArgs& a, int k, int lane, 
 __device__ __forceinline__ void mc_emit_voxel(const McArgs& a, int lane, int r, const McVoxel& v, int voxel_total, int voxel_offset, int ntri, int incl,
                                               unsigned long long tri_row, unsigned ok, const float* __restrict__ vl, const float* __restrict__ c_std, int64_t log_n,
                                               const float* __restrict__ vsd = nullptr) {
-    for (int j = lane; j < v.old_n; j += 64) a.tri_alive[v.old_s + j] = 0;
     int64_t n_new = voxel_total;
     if (voxel_offset + n_new > a.new_limit) n_new = a.new_limit > voxel_offset ? a.new_limit - voxel_offset : 0;      // truncated by max_n_triangles
     if (log_n + voxel_offset + n_new > a.max_triangles) n_new = a.max_triangles > log_n + voxel_offset ? a.max_triangles - (log_n + voxel_offset) : 0;
+    if (n_new <= 0) return;                 // cut off whole: nothing of it is kept, so its old batch stays (the reference's rule, include/difusion.h: max_triangles)
+    for (int j = lane; j < v.old_n; j += 64) a.tri_alive[v.old_s + j] = 0;
     if (lane == 0) {
         a.tri_start[v.slot] = (int)(log_n + voxel_offset);
         a.tri_n[v.slot] = (int)n_new;
@@ -958,13 +962,16 @@ struct TriScanFunctor {         // exclusive scan of the per-voxel triangle coun
         if (!valid_blocks) return;
         const int64_t log_n = counters[DIF_C_CACHE_KEPT];
         const int64_t slot = indexer[valid_blocks[k]];
-        const int old_n = tri_n[slot], old_s = tri_start[slot];
-        for (int j = 0; j < old_n; ++j) alive[old_s + j] = 0;
+        int old_n = tri_n[slot];
+        const int old_s = tri_start[slot];
         int64_t n_new = tri_count[k];
         if (offset + n_new > new_limit) n_new = new_limit > offset ? new_limit - offset : 0;          // truncated by max_n_triangles
         if (log_n + offset + n_new > capacity) n_new = capacity > log_n + offset ? capacity - (log_n + offset) : 0;
-        tri_start[slot] = (int)(log_n + offset);
-        tri_n[slot] = (int)n_new;
+        if (n_new > 0) {                    // (cut off whole: the voxel keeps its old batch, as in k_marching_cubes<true> and mc_emit_voxel)
+            for (int j = 0; j < old_n; ++j) alive[old_s + j] = 0;
+            tri_start[slot] = (int)(log_n + offset);
+            tri_n[slot] = (int)n_new;
+        } else old_n = 0;
         // dead-entry count: one atomic per wave, summed over the lanes that are in here together
         const unsigned long long here = __ballot(1);
         int dead = 0;

@@ -319,7 +319,12 @@ typedef struct dif_extract_buffers {
     int32_t* tri_count;             /* [max_voxels] triangles per dirty voxel                             */
     int32_t* tri_offset;            /* [max_voxels] exclusive prefix of tri_count                         */
     int32_t* block_tmp;             /* [4096] scan scratch                                                */
-    int64_t max_triangles;          /* map.py:581 max_n_triangles (per call)                              */
+    int64_t max_triangles;          /* map.py:581 max_n_triangles (per call): of the T triangles of a call (canonical order) the first
+                                     * min(T, max_triangles) are kept — and of those the ones the log still has room for (else DIF_C_OVERFLOW
+                                     * = 5).  The cache follows the reference's rule (map.py:703-714) on the KEPT triangles: a voxel's previous
+                                     * batch dies only when at least one of its new triangles is kept (tri_start / tri_n then name the kept
+                                     * part); a voxel whose new triangles are all cut off keeps its old batch, tri_start, tri_n, and adds
+                                     * nothing to DIF_C_CACHE_DEAD.  DIF_C_T reports the uncut T.                                          */
     /* Device-resident mesh cache (the reference keeps it in host numpy arrays and rebuilds them on every extract, map.py:703-714).
      * Here it is an append-only LOG: an extract appends its new triangles (canonical order) and kills the previous batch of
      * every voxel that produced >= 1 new triangle (`map->tri_start/tri_n` locate it) -- O(new + replaced) per extract instead
