@@ -261,9 +261,11 @@ __device__ __forceinline__ void focus_gather_body(const Geo& g, float enc_th, co
         i = (int64_t)(ty * 16 + (int)(threadIdx.x >> 4)) * img_w + tx * 16 + (int)(threadIdx.x & 15);
     }
     if (i == 0) {
-        int n = counters[DIF_C_N_OCCUPIED] + counters[DIF_C_ALLOC_NEW];
+        const int before = counters[DIF_C_N_OCCUPIED];
+        int n = before + counters[DIF_C_ALLOC_NEW];
         if (n > capacity) { n = (int)capacity; counters[DIF_C_OVERFLOW] = 1; }
         counters[DIF_C_N_OCCUPIED] = n;
+        counters[DIF_C_ALLOC_KEPT] = n - before;             // the slots handed out, for k_fuse: ALLOC_NEW keeps what the frame asked for
     }
     // spatial tiling: a 16 x 16 pixel tile none of whose 16 row pieces holds a point near the slab has nothing to gather (and no frame count to
     // restore: nothing of it was counted) — one byte per row piece instead of 5 bytes per pixel
@@ -606,7 +608,9 @@ __device__ __forceinline__ void fuse_body(const long long* __restrict__ rec, con
         }
     }
     const int n_upd = counters[DIF_C_C];
-    const int first_new = counters[DIF_C_N_OCCUPIED] - counters[DIF_C_ALLOC_NEW];      // this frame's new slots are already in the halo delta
+    // this frame's new slots are already in the halo delta.  (The slots before the call: n_occupied less the slots the allocation GOT — less
+    // ALLOC_NEW, what it asked for, puts the line too low when the capacity cut the allocation, and fused older boundary slots went unnoted.)
+    const int first_new = counters[DIF_C_N_OCCUPIED] - counters[DIF_C_ALLOC_KEPT];
     const int grp = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 5), ngrp = (int)((gridDim.x * blockDim.x) >> 5);
     const int f = threadIdx.x & 31;
     // where feature f sits in a record: the accumulator-fragment order of the tile's two halves (mlp.hip.h)

@@ -915,7 +915,7 @@ class DenseIndexedMap:
 
     def export_records(self, x_lo: int = None, x_hi: int = None, raw: bool = False) -> torch.Tensor:
         """(n, 32) int32 records of the allocated voxels with x index in [x_lo, x_hi) (default: all), slot order:
-        lin id (2 words) | w | w*z[29]  (raw=False, for additive merging)  or  z[29] itself (raw=True, exact copies)."""
+        lin id | flags (bit 0: dirty) | w | w*z[29]  (raw=False, for additive merging)  or  z[29] itself (raw=True, exact copies)."""
         x_lo = 0 if x_lo is None else max(0, int(x_lo))
         x_hi = self.n_xyz[0] if x_hi is None else min(self.n_xyz[0], int(x_hi))
         cap = max(self._n_occ_ub, 1)

@@ -64,7 +64,8 @@ enum {
     DIF_C_DEFERRED = 23,    /* 0, or the rows the per-voxel extract buffers would have needed when the last streaming extract (dirty_tot set, untiled,
                              * capacity > 4096) found them too small for min(7 K, n_occupied) voxels: that extract then changed NOTHING (dirty set kept,
                              * K = B = T = 0) — the caller grows dif_extract_buffers_t.max_voxels and the next extract meshes the accumulated dirty set */
-    DIF_C_STAMP = 31,       /* snapshots handed to the caller only (dif_extract_buffers_t.counters_out): the extract's `stamp`, written LAST        */
+    DIF_C_ALLOC_KEPT = 24,  /* slots the last integrate's allocation got: ALLOC_NEW cut by the capacity (n_occupied - ALLOC_KEPT = the slots before it)   */
+    DIF_C_STAMP = 31,      /* snapshots handed to the caller only (dif_extract_buffers_t.counters_out): the extract's `stamp`, written LAST        */
     DIF_C_COUNT = 32
 };
 

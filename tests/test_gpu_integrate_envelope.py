@@ -58,13 +58,17 @@ class Device:
     NAMES = ("latent", "obs", "dirty", "upd_list", "rec_dir", "indexer", "pos", "frame_count", "grid_bits", "grid_tot", "alloc_bits", "alloc_tot",
              "counters", "dirty_tot")
 
-    def __init__(self, pm: IC.IMap, model, prune_min: int, th: float = IC.TH):
+    def __init__(self, pm: IC.IMap, model, prune_min: int, th: float = IC.TH, own=None, halo: int = 0, list_cap: int = 0):
+        """own = (x_lo, x_hi), halo, list_cap: a slab of a spatially tiled map with its boundary change lists (tests/test_gpu_tiling_envelope.py)"""
         self.pm, self.model, cap, G = pm, model, pm.capacity, pm.grid ** 3
         self.words, self.n_blk = (G + 31) // 32, (cap + 255) // 256
         shapes = dict(latent=(cap * 29, torch.float32), obs=(cap, torch.float32), dirty=(cap, torch.uint8), upd_list=(cap, torch.int32),
                       rec_dir=(cap * 16, torch.int32), indexer=(G, torch.int64), pos=(cap, torch.int64), frame_count=(G, torch.int32),
                       grid_bits=(self.words, torch.int32), grid_tot=(1024, torch.int32), alloc_bits=(self.words, torch.int32),
                       alloc_tot=(1024, torch.int32), counters=(_lib.C_COUNT, torch.int32), dirty_tot=(self.n_blk, torch.int32))
+        if list_cap > 0:
+            shapes["halo_list"] = (2 * list_cap, torch.int32)
+            self.NAMES = Device.NAMES + ("halo_list",)
         self.guard = {}
         for name, (n, dt) in shapes.items():
             self.guard[name], view = _guarded(n, dt)
@@ -74,6 +78,10 @@ class Device:
         self.obs.copy_(_t(pm.obs))
         self.indexer.copy_(_t(pm.indexer))
         self.pos.copy_(_t(pm.pos))
+        self.dirty.copy_(_t(pm.dirty))                      # (with its block totals: the planted maps of the tiling tests carry dirty flags)
+        pad = np.zeros(self.n_blk * 256, dtype=np.int32)
+        pad[:cap] = pm.dirty
+        self.dirty_tot.copy_(_t(pad.reshape(-1, 256).sum(axis=1), np.int32))
         self.upd_list.fill_(-7)
         self.counters[_lib.C_N_OCCUPIED] = pm.n
         m = _lib.DifMap()
@@ -86,6 +94,11 @@ class Device:
                             ("rec_dir", "rec_dir"), ("upd_list", "upd_list"), ("dirty_tot", "dirty_tot"), ("alloc_bits", "alloc_bits"), ("alloc_tot", "alloc_tot")):
             setattr(m, field, _lib.ptr(getattr(self, name)))
         m.own_x_lo, m.own_x_hi, m.halo, m.frame_seq = 0, pm.grid, 0, 0          # one map, no halo lists, no pending export, one queue
+        if own is not None:
+            m.own_x_lo, m.own_x_hi, m.halo = int(own[0]), int(own[1]), int(halo)
+        if list_cap > 0:
+            self.halo_list.fill_(-9)
+            m.halo_list, m.halo_list_cap = _lib.ptr(self.halo_list), int(list_cap)
         self.cmap = m
 
     def state(self):
